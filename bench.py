@@ -19,7 +19,11 @@ available to host", as the reference's timer around render_image
 frame in host memory when each call returns).
 
 Workload (BASELINE.json configs[1]): examples/test1.yml at 3840x2160,
-recursion depth 5.  Extra line items on the same N GPUs: configs[2]
+recursion depth 5.  A plain run measures that line alone: it sets up, runs the
+untimed frames, times `--steps` frames, writes the last one with
+`--dump-outputs DIR` and prints the line.  With `--full` it adds the CPU
+baseline, the single-stream `kernel_ms` launches and, on the same N GPUs, the
+extra line items: configs[2]
 (test3.yml 3840x2160), the north_star scene (1024 spheres, 3840x2160, depth
 5), configs[3] (the same at 7680x4320) and configs[4] (4096 spheres + 8
 planes, 16384x16384, depth 8); at N=1 `host_visible` times the drop-in itself,
@@ -262,11 +266,35 @@ def render_streams(dev, n: int):
     return _RENDER_STREAMS[key]
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in DIR
+DUMP_SEED = 0x5EED
+
+
+def dump_frame(frame, out_dir) -> None:
+    """--dump-outputs: the (H, W, 4) uint8 RGBA frame of the last timed step as
+    DIR/frame.npy in float32.  A frame over DUMP_MAX_BYTES in float32 (the 4K
+    default is 133 MB) is written as a fixed sample of its pixels instead: the
+    sorted flat pixel indices numpy's default_rng(DUMP_SEED) draws without
+    replacement for this (H, W), rows in that order, shape (n, 4)."""
+    import numpy as np
+
+    frame = np.ascontiguousarray(frame)
+    H, W, ch = frame.shape
+    n_max = DUMP_MAX_BYTES // (ch * 4)
+    if H * W > n_max:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=n_max // 2, replace=False))
+        frame = frame.reshape(H * W, ch)[idx]
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "frame.npy", frame.astype(np.float32))
+
+
 def measure(workload: str, args, world: int, rank: int, local_rank: int, dev, cpu: bool, size=None,
-            steps=None, warmup=None, budget_s=None):
+            steps=None, warmup=None, budget_s=None, dump_dir=None):
     """Time `steps` frames of `workload` on this rank (after `warmup`), frame
     sharded over `world` ranks and gathered to rank 0.  `budget_s`: cap the
     frames so the timed region lasts about that long (slow extra lines).
+    `dump_dir`: rank 0 writes the last timed step's frame there (dump_frame).
     Returns the rank-0 result dict (None on other ranks)."""
     import torch
     import torch.distributed as dist
@@ -441,21 +469,32 @@ def measure(workload: str, args, world: int, rank: int, local_rank: int, dev, cp
             st_, px_ = ds.stream_status(s_.cuda_stream)
             _abi.check(st_, f"frame render (first erroring pixel {px_})")
 
+    if dump_dir is not None and rank == 0:  # the frame the last timed step left on rank 0
+        if native:
+            last = pipe.read_frame()
+        else:
+            last = (pipe.frame if pipe is not None else frame).cpu().numpy()
+        dump_frame(last, dump_dir)
+
     # Single-stream kernel time (one latency-sized launch after another, HIP
     # events on that stream): the time ONE launch of this rank's share takes on
     # an otherwise idle GPU (rocprofv3 of `--frames-in-flight 1` gives the same
-    # average).  Not the timed configuration (F frames in flight).
-    events = []
-    for _ in range(max(1, args.roofline_frames)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        render()
-        e1.record(stream)
-        events.append((e0, e1))
-    torch.cuda.synchronize(dev)
-    kernel_ms = sum(e0.elapsed_time(e1) for e0, e1 in events) / len(events)
+    # average).  Not the timed configuration (F frames in flight).  Launches of
+    # their own: with --full, and wherever frames are gathered (per_rank).
+    full = bool(getattr(args, "full", False))
+    kernel_ms = None
+    if full or gather:
+        events = []
+        for _ in range(max(1, args.roofline_frames)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            render()
+            e1.record(stream)
+            events.append((e0, e1))
+        torch.cuda.synchronize(dev)
+        kernel_ms = sum(e0.elapsed_time(e1) for e0, e1 in events) / len(events)
 
-    per_rank = gather_rank_times(elapsed, steps, kernel_ms, world, rank)
+    per_rank = gather_rank_times(elapsed, steps, kernel_ms, world, rank) if gather else None
     tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -511,14 +550,11 @@ def measure(workload: str, args, world: int, rank: int, local_rank: int, dev, cp
                               my_rows * W * 4, tex, alg_ops=rays_per_frame * ops_per_ray if split == world else 0.0)
     if split != world:  # --share diagnostic: the PMC figures are whole-frame ones
         roof.update({"achieved": None, "frac": None, "traffic": None, "basis": "--share diagnostic: not computed"})
-    ref_equiv = my_rays * ops_per_ray / (kernel_ms * 1e-3) / 1e12
     res = {
         "value": round(value, 3),
         "ms_per_step": round(frame_s * 1e3, 4),
         "steps": steps,
         "warmup": warmup,
-        "kernel_ms": round(kernel_ms, 4),
-        "kernel_ms_config": "one latency-sized launch at a time on one stream (rg_render_tiles_async), HIP events",
         "data": src,
         "settle_s": args.settle_s,
         "config": {"workload": label, "width": W, "height": H, "max_recursion_depth": scene.max_recursion_depth,
@@ -528,10 +564,14 @@ def measure(workload: str, args, world: int, rank: int, local_rank: int, dev, cp
         "rays_per_frame": {"primary": rays[0], "shadow": rays[1], "secondary": rays[2], "total": rays_per_frame},
         "roofline": roof,
         "roofline_hbm": roof_hbm,
+    }
+    if kernel_ms is not None:
+        res["kernel_ms"] = round(kernel_ms, 4)
+        res["kernel_ms_config"] = ("one latency-sized launch at a time on one stream (rg_render_tiles_async), "
+                                   "HIP events")
         # the reference's brute-force work (16 FP64 ops per sphere test, 14 per plane ...)
         # per single-stream launch: what the BVH and f32 pre-filter save, NOT a utilisation figure
-        "reference_equivalent_fp64_tops": round(ref_equiv, 3),
-    }
+        res["reference_equivalent_fp64_tops"] = round(my_rays * ops_per_ray / (kernel_ms * 1e-3) / 1e12, 3)
     if rccl is not None:
         res["rccl_nranks"] = rccl["nranks"]
         res["rccl"] = rccl
@@ -718,9 +758,16 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--workload", default="test1", help="test1 | test3 | synth<N>[p<planes>][d<depth>]")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the CPU baseline, the extra line items (configs[2..4], the "
+                         "north_star scene, host_visible) and the single-stream kernel_ms launches; a plain run "
+                         "sets up, warms up, times --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last one to DIR/frame.npy (float32; a fixed "
+                         "seeded sample of its pixels when the frame is over 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-north-star", "--no-extra", dest="no_extra", action="store_true",
-                    help="skip the extra line items (configs[2..4], the north_star scene, host_visible)")
+                    help="with --full: skip the extra line items (configs[2..4], the north_star scene, host_visible)")
     ap.add_argument("--extra", default="",
                     help="comma-separated subset of the extra lines to run (test3_4k, north_star_1024_spheres, "
                          "north_star_1024_spheres_8k, synth4096_16k, host_visible, host_visible_north_star); "
@@ -829,11 +876,11 @@ def main() -> None:
     else:
         torch.cuda.set_device(0)
     dev = torch.device("cuda", local_rank)
-    cpu = (not args.no_cpu_baseline) and world == 1
+    cpu = args.full and (not args.no_cpu_baseline) and world == 1
 
-    main_res = measure(args.workload, args, world, rank, local_rank, dev, cpu)
+    main_res = measure(args.workload, args, world, rank, local_rank, dev, cpu, dump_dir=args.dump_outputs)
     extras = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         want = set(filter(None, args.extra.split(","))) or None
         for key, wl, size, with_cpu in EXTRA_LINES:
             if want is not None and key not in want:

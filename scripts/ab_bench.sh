@@ -1,6 +1,7 @@
 #!/bin/bash
 # Interleaved A/B of library variants with bench.py's timed configuration.
 #   bash scripts/ab_bench.sh "<bench args>" rounds lib1 lib2 ...   (lib = path to a libraingun_hip.so)
+#   (the bench args decide what runs: add --full for the extra lines)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab

@@ -9,7 +9,7 @@
 #   tests[:selection]             pytest -m gpu (one process, per-test thread timeout)
 #   smoke                         __graft_entry__.smoke()
 #   bench[:args]                  bench.py (default: the driver configuration --steps 20 --warmup 5)
-#   benchfull                     the default bench.py run (every line, CPU baseline)
+#   benchfull                     bench.py --full (every line, CPU baseline)
 #   trace[:args]                  rocprofv3 --kernel-trace --stats of bench.py --no-extra
 #   ab:args:rounds:lib1,lib2..    interleaved A/B of library variants (scripts/ab_bench.sh)
 #   pmc:wl:w:h:steps              executed-work PMC of one bench line (scripts/pmc_work.sh)
@@ -55,7 +55,7 @@ print("bench", sys.argv[2], "ms", d["ms_per_step"], "frac", d.get("roofline", {}
 PY
       ;;
     benchfull)
-      timeout -k 10 600 python bench.py > "$O/bench_full.json" 2> "$O/bench_full.err" \
+      timeout -k 10 600 python bench.py --full > "$O/bench_full.json" 2> "$O/bench_full.err" \
         || { tail -20 "$O/bench_full.err"; exit 1; }
       tail -c 400 "$O/bench_full.json" | tee -a "$O/session.txt"; echo ;;
     trace)
@@ -79,7 +79,7 @@ PY
       wl=${a1:-test1}; iv=${a2:-1048576}
       (cd /tmp && timeout -k 10 240 rocprofv3 --pc-sampling-beta-enabled --pc-sampling-method stochastic \
         --pc-sampling-unit cycles --pc-sampling-interval "$iv" --output-format csv -d "$O/pcs_$wl" -o run -- \
-        python3 "$R/bench.py" --workload "$wl" --no-extra --no-cpu-baseline --roofline-frames 1 --steps 40 --warmup 2) \
+        python3 "$R/bench.py" --workload "$wl" --full --no-extra --no-cpu-baseline --roofline-frames 1 --steps 40 --warmup 2) \
         > "$O/pcs_$wl.log" 2>&1 || { tail -20 "$O/pcs_$wl.log"; exit 1; }
       ls -la "$O/pcs_$wl" | tee -a "$O/session.txt" ;;
     iter)

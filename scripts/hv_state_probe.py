@@ -33,7 +33,7 @@ def frames_ms(ds, buf, n=40):
 
 def main():
     between = sys.argv[1] if len(sys.argv) > 1 else "test3"
-    args = bench.parse_args(["--no-cpu-baseline"])
+    args = bench.parse_args(["--full", "--no-cpu-baseline"])
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     bench.measure("test1", args, 1, 0, 0, dev, False)  # what bench.py runs first

@@ -18,7 +18,7 @@ import bench  # noqa: E402
 def main():
     wls = sys.argv[1].split(",") if len(sys.argv) > 1 else ["test3", "test3"]
     extra = [a for a in sys.argv[2:]]
-    args = bench.parse_args(["--no-cpu-baseline", "--steps", "100", *extra])
+    args = bench.parse_args(["--full", "--no-cpu-baseline", "--steps", "100", *extra])
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     out = []

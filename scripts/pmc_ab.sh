@@ -12,7 +12,7 @@ for lib in "$@"; do
   OUT=$R/gpurun_out/pmcab/$W/$tag
   mkdir -p "$OUT"
   (cd /tmp && RAINGUN_HIP_LIB=$R/$lib timeout -s KILL 240 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d "$OUT" -o run -- \
-      python3 $R/bench.py --workload $W --no-extra --no-cpu-baseline --roofline-frames 1 --steps 3 --warmup 1 > "$OUT/log" 2>&1)
+      python3 $R/bench.py --workload $W --full --no-extra --no-cpu-baseline --roofline-frames 1 --steps 3 --warmup 1 > "$OUT/log" 2>&1)
   rc=$?
   echo "$W $lib rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/log"; exit $rc; fi

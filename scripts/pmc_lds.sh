@@ -3,7 +3,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=$PWD; W=${1:-synth1024}; OUT=$R/gpurun_out/pmclds/$W; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-BENCH="$R/bench.py --workload $W --no-extra --no-cpu-baseline --roofline-frames 1 --steps 3 --warmup 1"
+BENCH="$R/bench.py --workload $W --full --no-extra --no-cpu-baseline --roofline-frames 1 --steps 3 --warmup 1"
 i=0
 for pass in "SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_BRANCH"; do
   i=$((i+1))

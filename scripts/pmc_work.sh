@@ -13,7 +13,7 @@ OUT=$R/gpurun_out/pmcw/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-BENCH="$R/bench.py --workload $W --width $X --height $Y --no-extra --no-cpu-baseline --roofline-frames 1"
+BENCH="$R/bench.py --workload $W --width $X --height $Y --full --no-extra --no-cpu-baseline --roofline-frames 1"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
     python3 $BENCH --steps $STEPS --warmup 2 > "$OUT/trace.json" 2> "$OUT/trace.err"
 rc=$?; echo "$TAG trace rc=$rc"

@@ -91,3 +91,38 @@ def test_per_rank_times_reach_every_rank(tmp_path):
         assert [x["rank"] for x in res] == [0, 1]
         assert [x["ms_per_step"] for x in res] == [1.0, 2.0]
         assert [x["share_kernel_ms"] for x in res] == [0.5, 1.5]
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    sys.path.insert(0, str(BENCH.parent))
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert (a.full, a.dump_outputs) == (True, "d")
+
+
+def test_dump_frame_is_float32_bounded_and_repeatable(tmp_path):
+    import numpy as np
+
+    sys.path.insert(0, str(BENCH.parent))
+    import bench
+
+    rng = np.random.default_rng(1)
+    small = rng.integers(0, 256, (5, 7, 4), dtype=np.uint8)
+    bench.dump_frame(small, tmp_path / "small")
+    got = np.load(tmp_path / "small" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)  # a frame within the limit: whole
+    # one pixel over the limit: a sample, the same pixels on every run, in image order
+    n_max = bench.DUMP_MAX_BYTES // 16
+    H, W = 4, n_max // 4 + 1
+    big = np.zeros((H, W, 4), np.uint8)
+    big.reshape(-1)[:] = np.arange(big.size, dtype=np.uint32) % 251
+    bench.dump_frame(big, tmp_path / "a")
+    bench.dump_frame(big, tmp_path / "b")
+    a, b = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "b" / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (n_max // 2, 4) and a.nbytes <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(a, b)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(H * W, size=n_max // 2, replace=False))
+    assert np.array_equal(a, big.reshape(-1, 4)[idx])
