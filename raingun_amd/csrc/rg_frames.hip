@@ -22,8 +22,6 @@
 
 namespace {
 
-bool ok(hipError_t e) { return e == hipSuccess; }
-
 // The gathered parts travel as packed RGB, 3 B per pixel: alpha is always
 // 255 (color.rs rgba()), so a quarter of every gather's bytes over xGMI carried
 // no information.  Non-root ranks pack their part after the render; the root
@@ -336,9 +334,15 @@ rg_status rg_frames_step(rg_frames *f) {
     hipStream_t rs = f->render[b];
     if (f->k >= (unsigned long long)f->depth && !ok(hipStreamWaitEvent(rs, f->done[b], 0))) return RG_ERR_DEVICE;
     // (one of several frames in flight: the heavy path sizes its grid for throughput)
-    rg_status st = rg_launch_tiles(f->scene, f->w, f->h, &f->tiling, static_cast<uint8_t *>(f->parts[b]), nullptr, rs,
-                                   nullptr, nullptr, false, nullptr, 0, nullptr, 3, false, true, 0, 0xFFFFFFFFu, false,
-                                   f->rank == 0 ? f->root : 1u);
+    rg_launch_desc d;
+    d.width = f->w;
+    d.height = f->h;
+    d.tiling = f->tiling;
+    d.rgba = static_cast<uint8_t *>(f->parts[b]);
+    d.stream = rs;
+    d.pipelined = true;
+    d.tile_group = f->rank == 0 ? f->root : 1u;
+    rg_status st = rg_launch_tiles(f->scene, d);
     if (st != RG_OK) return st;
     // off the root the part travels packed (3 B per pixel) in its batch's send buffer;
     // the root's own part is read in place

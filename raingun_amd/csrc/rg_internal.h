@@ -1,18 +1,23 @@
 // rg_internal.h — host-side state behind the opaque rg_scene handle, shared
-// by rg_capi.hip (scene upload, launches, host-visible frames, streaming),
-// rg_frames.hip (frames in flight over N processes) and rg_multi.hip (one
-// process driving N devices).  Not part of the ABI.
+// by rg_scene.hip (scene upload, kernel arguments), rg_launch.hip (per-stream
+// launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
+// streaming, debug setters), rg_frames.hip (frames in flight over N processes)
+// and rg_multi.hip (one process driving N devices).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <initializer_list>
 #include <memory>
 #include <vector>
 
 #include "../../include/raingun.h"
 #include "../../include/raingun_debug.h"
+#include "rg_copy_pool.h"
 #include "rg_device.h"
 #include "rg_lightbuf_ray.h"
+
+inline bool ok(hipError_t e) { return e == hipSuccess; }
 
 // Per-stream launch state (ray counters, tile-queue heads, error words, tile
 // ordering scratch, deep frame buffer, timing events).  Launches on distinct
@@ -50,7 +55,7 @@ struct rg_launch_ctx {
     void *deep = nullptr;  // frames for depths above the compiled arrays (rg_kernels.hip FrameStack<0>)
     size_t deep_bytes = 0;
     double *prim = nullptr;  // sensor x per column then sensor y per row (RgKernelArgs::prim_sx / prim_sy)
-    size_t prim_cap = 0;     // doubles
+    size_t prim_cap = 0;     // bytes
     uint32_t prim_w = 0, prim_h = 0;
     double prim_fov = 0.0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -74,31 +79,6 @@ struct rg_launch_ctx {
 // 64x1 2.66: profiles/r05/s13, s14, s15)
 #define RG_HOST_TILE_WLOG 4
 #endif
-#ifndef RG_COPY_HELPERS
-#define RG_COPY_HELPERS 3       // helper threads of the pageable host copy (plus the calling thread)
-#endif
-
-// Parallel host memcpy for frames delivered into PAGEABLE caller memory: one
-// thread moves a band out of pinned staging at ~10-17 GB/s, a third of what
-// PCIe delivers (~56 GB/s), so the band is split over the calling thread and
-// RG_COPY_HELPERS helpers.  Helpers spin while a render call is in progress
-// (fork/join per band in ~1 us) and sleep between calls.
-class rg_copy_pool {
-  public:
-    explicit rg_copy_pool(int helpers);
-    ~rg_copy_pool();
-    rg_copy_pool(const rg_copy_pool &) = delete;
-    rg_copy_pool &operator=(const rg_copy_pool &) = delete;
-    void begin();  // a render call starts: helpers spin
-    void end();    // ... ends: helpers sleep
-    void copy(void *dst, const void *src, size_t bytes);  // blocking, split over all threads
-
-  private:
-    void run(int id);
-    struct Impl;
-    Impl *p_;
-};
-
 // Resources of the host-visible paths (rg_render_image / rg_render_tiles /
 // rg_render_stream), owned by the scene and reused across calls.
 struct rg_image_res {
@@ -185,13 +165,13 @@ struct rg_scene {
     int tile_order = -1;  // expensive tiles first (rg_kernels.hip "tile ordering"): -1 auto (heavy path), 0, 1
     int image_bands = 0;  // host-visible frames: 0 auto, -1 one launch writing host memory, -2 split, 1..16 row bands
     int host_split_pct = 0;  // -2 (split): percent of the frame's rows rendered into device memory + DMA (0: default)
-    mutable int split_fail_a = 0;
+    mutable int split_fail_a = 0;  // debug: the next N split renders report part A's launch as failed (rg_debug_fail_split_a)
     // light-path host frames (rg_debug_set_host_ring): LDS-ring flush size and queue group of small
-    // (< RG_RING_BIG_TILES tiles) and big launches; rg_render_multi's automatic mode runs light
-    // scenes' shares as one launch per device (else bands + DMA)
+    // (< RG_RING_BIG_TILES tiles) and big launches
     int ring_flush_small = RG_RING_FLUSH_SMALL, ring_group_small = RG_RING_GROUP_SMALL;
     int ring_flush_big = RG_RING_FLUSH_BIG, ring_group_big = RG_RING_GROUP_BIG;
-    bool multi_light_one = RG_MULTI_LIGHT_ONE != 0;  // debug: the next N split renders report part A's launch as failed (rg_debug_fail_split_a)
+    // rg_render_multi's automatic mode renders each light-scene device share as one launch (else bands + DMA)
+    bool multi_light_one = RG_MULTI_LIGHT_ONE != 0;
     int host_tile_wlog = RG_HOST_TILE_WLOG;  // tile shape of the one-launch host-visible path
     bool host_tile_forced = false;           // set by rg_debug_set_host_tile_shape (else light scenes: 64x1)
     // rg_render_multi (rg_debug_set_multi): 0 each device copies its rows to the host, 1 RCCL gather;
@@ -221,24 +201,35 @@ void rg_frames_detach_scene(rg_frames *f);
 // Kernel arguments of a scene (tables, LDS arena, frame constants).
 RgKernelArgs rg_make_args(const rg_scene *s);
 
-// Enqueue one tiled render on `stream` (the body of rg_render_tiles_async).
-// snap (nullable, host memory, pinned for a truly asynchronous copy): the
-// launch's 4 counter words (rays by class, error key) are copied there after
-// the kernel.  ctx_out (nullable): the stream's launch context.  timed: record
-// the context's ev0/ev1 around the launch (kernel_ms).
-rg_status rg_launch_tiles(const rg_scene *s, uint32_t width, uint32_t height, const rg_tiling *tiling,
-                          uint8_t *rgba_dev, float *rgb_dev, hipStream_t stream, unsigned long long *snap,
-                          rg_launch_ctx **ctx_out, bool timed = false, uint32_t *tile_flags = nullptr,
-                          uint32_t frame_seq = 0, const uint32_t *cancel = nullptr, uint32_t tile_wlog = 3,
-                          bool host_frame = false,   // host_frame: rgba_dev is page-locked host memory
-                          bool pipelined = false,    // frames in flight: size the grid for throughput
-                          // a band of the tiling's selection: selected tiles [tile_first, tile_first + tile_count),
-                          // rgba_dev / rgb_dev pointing at tile_first's first row
-                          uint32_t tile_first = 0, uint32_t tile_count = 0xFFFFFFFFu,
-                          // host_frame only: rgba_dev is the whole image, pixels go to their image rows
-                          bool image_rows = false,
-                          // groups of tile_group consecutive image tiles per stride (RgKernelArgs::tile_group)
-                          uint32_t tile_group = 1);
+// One tiled render (rg_launch_tiles); the member initialisers are the defaults.
+struct rg_launch_desc {
+    uint32_t width = 0, height = 0;
+    rg_tiling tiling{};
+    uint8_t *rgba = nullptr;  // device memory, or page-locked host memory when host_frame
+    float *rgb = nullptr;     // nullable
+    hipStream_t stream = nullptr;
+    // nullable, host memory, pinned for a truly asynchronous copy: the launch's 4 counter
+    // words (rays by class, error key) are copied there after the kernel
+    unsigned long long *snap = nullptr;
+    bool timed = false;  // record the context's ev0/ev1 around the launch (kernel_ms)
+    // per-tile publication words, the sequence number they carry and the cancellation word
+    // (RgKernelArgs::tile_flags / frame_seq / cancel), all nullable
+    uint32_t *tile_flags = nullptr;
+    uint32_t frame_seq = 0;
+    const uint32_t *cancel = nullptr;
+    uint32_t tile_wlog = 3;   // tile shape (RgKernelArgs::tile_wlog), 3: 8x8
+    bool host_frame = false;  // rgba is page-locked host memory
+    bool pipelined = false;   // frames in flight: size the grid for throughput
+    bool image_rows = false;  // host_frame only: rgba is the whole image, pixels go to their image rows
+    // a band of the tiling's selection: selected tiles [tile_first, tile_first + tile_count),
+    // rgba / rgb pointing at tile_first's first row
+    uint32_t tile_first = 0, tile_count = 0xFFFFFFFFu;
+    uint32_t tile_group = 1;  // groups of tile_group consecutive image tiles per stride (RgKernelArgs::tile_group)
+};
+
+// Enqueue one tiled render on d.stream (the body of rg_render_tiles_async).
+// ctx_out (nullable): the stream's launch context.
+rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx **ctx_out = nullptr);
 
 // Rows a tiling selects when its tiles come in groups of `group` consecutive image tiles per
 // stride (group 1: rg_tiling_rows); 0 for an invalid tiling or group (offset + group > stride).
@@ -263,3 +254,43 @@ void rg_sync_settings(rg_scene *dst, const rg_scene *src);  // depth, path, BVH,
 
 // rg_multi.hip: free the scene's multi-GPU resources (replicas, communicators).
 void rg_multi_release(const rg_scene *s);
+
+// Shared between the library's own files only: not exported.
+#pragma GCC visibility push(hidden)
+
+// rg_launch.hip: the launch context of `stream`, created on first use (nullptr: out of
+// memory / device error), and its destruction.
+rg_launch_ctx *rg_ctx_for(const rg_scene *s, hipStream_t stream);
+void rg_ctx_destroy(rg_launch_ctx *c);
+bool rg_tiling_valid(const rg_tiling *t);
+
+// Grow-only buffers under one capacity: nothing if want <= cap; else free, null, allocate,
+// set the capacity.  RG_MEM_DEVICE: hipMalloc; RG_MEM_PINNED: hipHostMallocDefault;
+// RG_MEM_PINNED_ZEROED: hipHostMallocCoherent, zeroed.  clear_error: a failed allocation's
+// error is cleared from the runtime (hipGetLastError).
+enum rg_mem { RG_MEM_DEVICE, RG_MEM_PINNED, RG_MEM_PINNED_ZEROED };
+struct rg_grow_buf {
+    void **p;
+    size_t bytes;
+    template <class T>
+    rg_grow_buf(T *&q, size_t n) : p(reinterpret_cast<void **>(&q)), bytes(n) {}
+};
+rg_status rg_grow(rg_mem kind, size_t &cap, size_t want, std::initializer_list<rg_grow_buf> bufs,
+                  bool clear_error = true);
+template <class T>
+rg_status rg_grow(rg_mem kind, T *&p, size_t &cap, size_t bytes) {  // one buffer, capacity in bytes
+    return rg_grow(kind, cap, bytes, {{p, bytes}});
+}
+
+// rg_scene.hip: is the scene on the heavy path (rg_device.h rg_heavy_path)?
+bool rg_scene_heavy(const rg_scene *s);
+// rg_scene.hip: the LDS arena of launch args `a` as one device image (light path:
+// RgKernelArgs::lds_blob); nullptr if it cannot be made.
+const void *rg_lds_blob_for(const rg_scene *s, const RgKernelArgs &a);
+
+// rg_capi.hip: tile shape (RgKernelArgs::tile_wlog) of the one-launch host-visible paths.
+uint32_t rg_host_tile_wlog(const rg_scene *s);
+// rg_capi.hip: free the host-visible paths' resources.
+void rg_image_res_release(rg_image_res &r);
+
+#pragma GCC visibility pop

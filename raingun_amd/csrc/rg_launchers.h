@@ -1,0 +1,17 @@
+// rg_launchers.h — the launchers rg_kernels.hip defines for the host side
+// (rg_launch.hip, rg_capi.hip).  rg_kernels.hip does not include this header:
+// a change to a launcher's signature there is repeated here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rg_device.h"
+
+extern "C" hipError_t rg_launch_render(const RgKernelArgs *a, int maxd, hipStream_t stream);
+extern "C" int rg_host_array_frames(void);
+extern "C" hipError_t rg_render_grid_threads(const RgKernelArgs *a, int maxd, size_t *threads);
+extern "C" int rg_max_array_frames(void);
+extern "C" int rg_launch_global_frames(const RgKernelArgs *a, int maxd);
+extern "C" hipError_t rg_launch_tile_order(const RgKernelArgs *a, uint32_t *scratch, uint32_t *perm, hipStream_t stream);
+extern "C" size_t rg_tile_order_scratch_words(uint32_t ntiles);
+extern "C" hipError_t rg_launch_trace(const RgKernelArgs *a, const double *rays, uint32_t n, double *dist,
+                                      int32_t *body, hipStream_t stream);

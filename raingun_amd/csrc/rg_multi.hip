@@ -54,8 +54,6 @@ size_t rg_packed_slot_bytes(uint32_t slot_rows, uint32_t width);
 
 namespace {
 
-bool ok(hipError_t e) { return e == hipSuccess; }
-
 // ---------------------------------------------------------------- RCCL, loaded at run time
 typedef int (*pfn_comm_init_all)(void **comms, int ndev, const int *devlist);
 typedef int (*pfn_comm_destroy)(void *comm);
@@ -359,15 +357,25 @@ rg_status merge_snaps(const rg_multi_res *m, int per_dev, rg_stats *stats) {
     return err;
 }
 
+// A launch of device i's share of the frame: tile_rows-row tiles dealt round-robin, tile t -> device t % n.
+rg_launch_desc share_launch(const rg_multi_res *m, int i, void *rgba, hipStream_t stream, unsigned long long *snap) {
+    rg_launch_desc d;
+    d.width = m->w;
+    d.height = m->h;
+    d.tiling = {m->T, (uint32_t)m->n, (uint32_t)i};
+    d.rgba = static_cast<uint8_t *>(rgba);
+    d.stream = stream;
+    d.snap = snap;
+    return d;
+}
+
 // RCCL path: render, ONE grouped gather to device 0, re-interleave, one copy to the host.
 rg_status render_gather(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, rg_stats *stats) {
     const uint32_t W = m->w, H = m->h, T = m->T;
     const int n = m->n;
     if (!ok(hipSetDevice(m->devs[0])) || !ok(hipEventRecord(m->ev0, m->streams[0]))) return RG_ERR_DEVICE;
     for (int i = 0; i < n; ++i) {
-        const rg_tiling t = {T, (uint32_t)n, (uint32_t)i};
-        rg_status st = rg_launch_tiles(m->reps[i], W, H, &t, static_cast<uint8_t *>(m->parts[i]), nullptr,
-                                       m->streams[i], m->snap + 4 * i, nullptr);
+        rg_status st = rg_launch_tiles(m->reps[i], share_launch(m, i, m->parts[i], m->streams[i], m->snap + 4 * i));
         if (st != RG_OK) return st;
         if (i > 0 && !ok(rg_launch_pack_rgb(m->parts[i], m->packed[i], (size_t)m->slot_rows * W, m->streams[i])))
             return RG_ERR_DEVICE;
@@ -404,11 +412,9 @@ rg_status render_gather(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
 // no band waits for a DMA -- a device's time is its render latency or its rows'
 // PCIe time, whichever is longer.
 rg_status render_direct_one(const rg_scene *s, rg_multi_res *m, uint8_t *dst, rg_stats *stats) {
-    const uint32_t W = m->w, H = m->h, T = m->T;
     const int n = m->n;
-    const size_t frame_bytes = (size_t)H * W * 4;
-    const bool light = !rg_heavy_path(rg_make_args(s));
-    const uint32_t wl = (uint32_t)(s->host_tile_forced || !light ? s->host_tile_wlog : RG_HOST_TILE_WLOG_LIGHT);
+    const size_t frame_bytes = (size_t)m->h * m->w * 4;
+    const uint32_t wl = rg_host_tile_wlog(s);
     if (!ok(hipSetDevice(m->devs[0])) || !ok(hipEventRecord(m->ev0, m->streams[0]))) return RG_ERR_DEVICE;
     for (int i = 0; i < n; ++i) {
         unsigned long long *snap = m->snap + 4 * i;
@@ -419,10 +425,11 @@ rg_status render_direct_one(const rg_scene *s, rg_multi_res *m, uint8_t *dst, rg
         if (!ok(hipSetDevice(m->devs[i]))) return RG_ERR_DEVICE;
         void *d = rg_host_device_ptr(dst, frame_bytes);  // registered portable: mapped on every device
         if (!d) return RG_ERR_DEVICE;
-        const rg_tiling t = {T, (uint32_t)n, (uint32_t)i};
-        const rg_status st = rg_launch_tiles(m->reps[i], W, H, &t, static_cast<uint8_t *>(d), nullptr, m->streams[i],
-                                             snap, nullptr, false, nullptr, 0, nullptr, wl, true, false, 0,
-                                             0xFFFFFFFFu, true);
+        rg_launch_desc ld = share_launch(m, i, d, m->streams[i], snap);
+        ld.tile_wlog = wl;
+        ld.host_frame = true;
+        ld.image_rows = true;
+        const rg_status st = rg_launch_tiles(m->reps[i], ld);
         if (st != RG_OK) return st;
     }
     (void)hipSetDevice(m->devs[0]);
@@ -459,7 +466,7 @@ rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
     // 0.20 ms, the copy now overlapping the render: profiles/r06/s6; with 16-tile groups it was
     // 0.49-0.52 ms).  Only when every device can store into the frame: otherwise the
     // banded DMA copies, which work for any page-locked buffer.
-    if (!pageable && (s->multi_bands < 0 || (s->multi_bands == 0 && (s->multi_light_one || rg_heavy_path(rg_make_args(s))))) &&
+    if (!pageable && (s->multi_bands < 0 || (s->multi_bands == 0 && (s->multi_light_one || rg_scene_heavy(s)))) &&
         mapped_on_all(m, dst, frame_bytes))
         return render_direct_one(s, m, dst, stats);
     if (pageable) {
@@ -480,7 +487,6 @@ rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
     if (!ok(hipSetDevice(m->devs[0])) || !ok(hipEventRecord(m->ev0, m->streams[0]))) return RG_ERR_DEVICE;
     for (int b = 0; b < K; ++b) {
         for (int i = 0; i < n; ++i) {
-            const rg_tiling t = {T, (uint32_t)n, (uint32_t)i};
             const uint32_t sel = (tiles > (uint32_t)i) ? (tiles - (uint32_t)i + (uint32_t)n - 1) / (uint32_t)n : 0u;
             uint32_t j0 = std::min(sel, (uint32_t)b * J), j1 = std::min(sel, j0 + J);
             if (s->multi_only_rank >= 0 && i != s->multi_only_rank) j1 = j0;  // timeline rehearsal of one device
@@ -494,8 +500,10 @@ rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
                 continue;
             }
             uint8_t *part = static_cast<uint8_t *>(m->parts[i]) + (size_t)j0 * T * row4;
-            rg_status st = rg_launch_tiles(m->reps[i], W, H, &t, part, nullptr, rs, snap, nullptr, false, nullptr,
-                                           0, nullptr, 3, false, false, j0, j1 - j0);
+            rg_launch_desc ld = share_launch(m, i, part, rs, snap);
+            ld.tile_first = j0;
+            ld.tile_count = j1 - j0;
+            rg_status st = rg_launch_tiles(m->reps[i], ld);
             if (st != RG_OK) return st;
             if (!ok(hipEventRecord(m->ev_band[i][b], rs)) || !ok(hipStreamWaitEvent(m->copies[i], m->ev_band[i][b], 0)))
                 return RG_ERR_DEVICE;
@@ -526,11 +534,7 @@ rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
         // band b's image rows [b J n T, (b + 1) J n T) are complete once every device copied its part
         rg_image_res &img = s->img;
         if (!img.pool) img.pool = std::make_shared<rg_copy_pool>(RG_COPY_HELPERS);
-        struct Active {
-            rg_copy_pool &p;
-            explicit Active(rg_copy_pool &q) : p(q) { p.begin(); }
-            ~Active() { p.end(); }
-        } active(*img.pool);
+        rg_copy_pool::Active active(*img.pool);
         for (int b = 0; b < K; ++b) {
             for (int i = 0; i < n; ++i)
                 if (!ok(hipSetDevice(m->devs[i])) || !ok(hipEventSynchronize(m->ev_copy[i][b]))) return RG_ERR_DEVICE;

@@ -59,7 +59,7 @@ static void cross(const double a[3], const double b[3], double c[3]) {
 struct Light {
     int kind;            // RG_LIGHT_DIRECTIONAL / RG_LIGHT_SPHERICAL
     double v[3];         // direction / position
-    double dn[3];        // normalize(-direction), as rg_capi.hip computes it
+    double dn[3];        // normalize(-direction), as rg_scene.hip computes it
     RgLightBufBuild lb;
     bool has = false;
 };
