@@ -185,6 +185,39 @@ rg_status rg_scene_set_max_depth(rg_scene *scene, uint32_t max_recursion_depth);
 rg_status rg_render_image(const rg_scene *scene, uint32_t width, uint32_t height,
                           uint8_t *rgba_out, rg_stats *stats);
 
+/* rg_render_image with samples x samples rays per pixel on a regular sub-pixel grid,
+ * box-filtered (supersampled anti-aliasing; samples 1..8).  The rays are those of the
+ * samples*width x samples*height frame (ray.rs:43-49 puts them exactly on the sub-pixel
+ * grid).  Per pixel and channel, in f32: every sample s is clamped (s if 0 <= s <= 1, 1 if
+ * s > 1, else 0: negatives and NaN), the clamped samples are added one by one to 0, sample
+ * rows outer, columns inner, the sum is divided by samples*samples, and the byte is
+ * `(mean * 255.0) as u8` (color.rs:32-37) with alpha 255.  `rgb_out` (nullable, host,
+ * width*height*3 floats) receives the means.  samples == 1 gives the bytes of
+ * rg_render_image.  `stats` counts the rays of every sample; on a device error the frame
+ * is still delivered, the status is the reference's panic code and stats->error_pixel is
+ * the output pixel that contains the lowest-index failing sample.  RG_ERR_INVALID_ARGUMENT
+ * for null pointers, zero sizes, samples outside 1..8 or a sample frame of 2^32 pixels or
+ * more; RG_ERR_PORTRAIT for width < height. */
+rg_status rg_render_image_aa(const rg_scene *scene, uint32_t width, uint32_t height, uint32_t samples,
+                             uint8_t *rgba_out, float *rgb_out, rg_stats *stats);
+
+/* Device-resident rg_render_image_aa: `rgba_dev` (width*height*4 bytes) and `rgb_dev`
+ * (nullable, width*height*3 floats) are device pointers on the scene's device.  The work is
+ * ordered after everything enqueued on `stream` (a hipStream_t; NULL = null stream) so far,
+ * and later work on `stream` is ordered after it; in between it runs on two streams of the
+ * scene's own.  Asynchronous unless `stats` is non-NULL, in which case the call
+ * synchronises `stream` and fills ray counts, time and errors (as rg_render_tiles_async).
+ * Without `stats` device errors are not reported (rg_stream_status does not see this
+ * call's launches).  Calls on one scene must come from one host thread at a time. */
+rg_status rg_render_aa_async(const rg_scene *scene, uint32_t width, uint32_t height, uint32_t samples,
+                             uint8_t *rgba_dev, float *rgb_dev, void *stream, rg_stats *stats);
+
+/* The resolve of rg_render_image_aa alone, on `device`, host buffers: `rgb_in` is
+ * (samples*height) x (samples*width) x 3 floats, row-major; `rgba_out` width*height*4
+ * bytes; `rgb_out` nullable, width*height*3 floats.  Blocking. */
+rg_status rg_resolve_box(int32_t device, const float *rgb_in, uint32_t width, uint32_t height,
+                         uint32_t samples, uint8_t *rgba_out, float *rgb_out);
+
 /* Page-lock a caller buffer (hipHostRegister) so rg_render_image / rg_render_tiles
  * / rg_render_multi DMA straight into it; unregister before freeing it.  Optional:
  * pageable buffers work too (staged).  A Rust caller registers its

@@ -95,6 +95,12 @@ rg_status rg_debug_set_host_ring(rg_scene *scene, int32_t flush_small, int32_t g
  * scenes, 64x1 for light-path scenes).  Device-resident renders always use 8x8. */
 rg_status rg_debug_set_host_tile_shape(rg_scene *scene, int32_t tile_wlog);
 
+/* Supersampled frames (rg_render_image_aa / rg_render_aa_async) render and resolve in
+ * bands of `rows` output rows (samples * rows sample rows); 0 (default) = automatic: the
+ * band whose samples (16 B each) fit 64 MiB, a multiple of 8 rows, at least 8.  Tests force
+ * small bands so that small frames span several.  Results are identical for every value. */
+rg_status rg_debug_set_aa_band_rows(rg_scene *scene, int32_t rows);
+
 /* rg_render_multi: mode 0 (default) = every device delivers its rows of the
  * frame to the host buffer itself, over its own PCIe link: `bands` = -1 one
  * launch per device whose kernel stores its rows straight into a page-locked

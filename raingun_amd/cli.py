@@ -1,12 +1,15 @@
 """`raingun` command line, mirroring the reference's src/main.rs + src/render.rs.
 
-    python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [-o FILE] FILE
+    python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
 (main.rs:74-75, 119-123); --hd / --4k set 1920x1080 / 3840x2160 and override
 each other (the last one wins); explicit --width/--height override presets
-(but not --draft, which clap treats as overriding them, main.rs:47-54).  The
+(but not --draft, which clap treats as overriding them, main.rs:47-54).
+`--samples N` (1..8, default 1; not in the reference) renders N x N rays per
+pixel on the regular sub-pixel grid and box-filters them (rg_render_image_aa);
+--draft leaves it alone.  The
 render itself runs on the GPU (rg_render_image); the scene is loaded and the
 PNG written by the native host layer (libraingun_host.so), and the timing line matches
 print_render_message (render.rs:218-244).  `--preview` (piston window) is not
@@ -29,6 +32,7 @@ class RenderOptions:          # render.rs:32-46
     width: int = 800
     height: int = 600
     max_recursion_depth: Optional[int] = None
+    samples: int = 1          # N x N rays per pixel (--samples; not in the reference)
 
 
 class _LastWins(argparse.Action):
@@ -55,12 +59,18 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("-o", "--output", metavar="FILENAME",
                    help='Where to save the rendered image. Defaults to input filename with ".png" extension.')
     p.add_argument("--gpu", type=int, default=0, help="HIP device to render on.")
+    p.add_argument("--samples", metavar="N",
+                   help="Anti-aliasing: N x N rays per pixel on a regular grid, box-filtered (1..8, default 1).")
     p.add_argument("input", metavar="FILE", help="The scene definition file, in YAML format.")
     return p
 
 
 def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
     o = RenderOptions()
+    if ns.samples is not None:
+        o.samples = _parse_u32(ns.samples, "Could not parse samples")
+        if not 1 <= o.samples <= 8:
+            raise SystemExit("samples must be between 1 and 8")
     if ns.draft:
         o.max_recursion_depth = 4
     elif ns.hd:
@@ -135,7 +145,10 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
 
     ds = DeviceScene(scene, device=ns.gpu)
     t0 = time.perf_counter()                     # render.rs:54-56
-    img = ds.render_image(opts.width, opts.height)
+    if opts.samples > 1:
+        img = ds.render_image_aa(opts.width, opts.height, opts.samples)
+    else:
+        img = ds.render_image(opts.width, opts.height)
     t1 = time.perf_counter()
     output_path.write_bytes(encode_png(img))     # render.rs:58
     t2 = time.perf_counter()

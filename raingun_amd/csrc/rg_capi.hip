@@ -5,7 +5,8 @@
 // the batch closest-hit query and the debug setters.  The scene is in
 // rg_scene.hip, the tiled launch every path here goes through in
 // rg_launch.hip, the pageable-frame copy pool in rg_copy_pool.cpp, the
-// single-process multi-GPU entry (rg_render_multi) in rg_multi.hip.  No
+// single-process multi-GPU entry (rg_render_multi) in rg_multi.hip, the
+// supersampled frames (rg_render_image_aa) in rg_aa.hip.  No
 // exception or abort crosses the ABI.
 #include <hip/hip_runtime.h>
 
@@ -217,8 +218,11 @@ host_grid host_tile_grid(uint32_t W, uint32_t rows, uint32_t wlog) {
     return {TH, tiles_x, tile_rows, tiles_x * tile_rows};
 }
 
+}  // namespace
+
 // Ray counts summed over n band snapshots (4 words each); the first erroring snapshot in index
 // order gives the status and the pixel (bands in row order: it holds the lowest erroring pixel).
+// Shared with rg_aa.hip.
 rg_status rg_merge_band_snaps(const unsigned long long *snap, int n, rg_stats *total) {
     std::memset(total, 0, sizeof *total);
     total->error_pixel = -1;
@@ -236,6 +240,8 @@ rg_status rg_merge_band_snaps(const unsigned long long *snap, int n, rg_stats *t
     }
     return err;
 }
+
+namespace {
 
 // Host-visible frame in ONE launch, no device framebuffer and no copy engine:
 // the kernel's pixel stores go straight over PCIe into page-locked host memory

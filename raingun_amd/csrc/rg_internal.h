@@ -103,6 +103,35 @@ struct rg_image_res {
     unsigned long long *h_snap = nullptr;  // pinned: 4 counter words per band
 };
 
+#ifndef RG_AA_SLOT_BYTES
+// supersampled frames (rg_aa.hip): the scratch of one band of samples (RGBA8 + f32 RGB,
+// 16 B per sample) stays within this; two such slots, one per render stream
+#define RG_AA_SLOT_BYTES ((size_t)64 << 20)
+#endif
+#define RG_AA_MIN_BAND_ROWS 8   // output rows per band at least (automatic choice)
+#define RG_AA_MAX_SAMPLES 8     // samples per pixel side
+// Resources of the supersampled paths (rg_render_image_aa / rg_render_aa_async), owned by
+// the scene and reused across calls.
+struct rg_aa_res {
+    std::shared_ptr<rg_copy_pool> pool;      // pageable destinations (created on first use)
+    hipStream_t rs[2] = {nullptr, nullptr};  // render + resolve streams (bands alternate)
+    hipStream_t cs = nullptr;                // device-to-host copies
+    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_join = nullptr, ev_fork = nullptr;
+    std::vector<hipEvent_t> ev_done, ev_copy;  // per band: resolved, copied
+    // per render stream, one band of samples: RGBA8 (the render kernel always writes it) and f32 RGB
+    void *slot_rgba[2] = {nullptr, nullptr};
+    void *slot_rgb[2] = {nullptr, nullptr};
+    size_t slot_cap[2] = {0, 0};  // samples
+    void *d_rgba = nullptr;       // the resolved frame of the host entry
+    size_t d_rgba_cap = 0;
+    void *d_rgb = nullptr;
+    size_t d_rgb_cap = 0;
+    void *h_stage = nullptr;  // pinned staging ring (pageable destinations)
+    size_t h_stage_cap = 0;
+    unsigned long long *h_snap = nullptr;  // pinned: 4 counter words per band
+    size_t h_snap_cap = 0;                 // bytes
+};
+
 // Everything rg_scene_create uploads, as host tables (kept for replicas on
 // other devices: rg_render_multi).
 struct rg_host_tables {
@@ -189,6 +218,8 @@ struct rg_scene {
     mutable std::vector<rg_launch_ctx *> ctxs;  // one per stream used
     mutable rg_launch_ctx *last = nullptr;       // the context of the latest launch (rg_debug_counters)
     mutable rg_image_res img;
+    int aa_band_rows = 0;  // supersampled frames: output rows per band (rg_debug_set_aa_band_rows), 0 automatic
+    mutable rg_aa_res aa;
     mutable rg_multi_res *multi = nullptr;
     // frame pipelines built on this scene: a scene destroyed first detaches them
     // (rg_frames_destroy then no longer touches it), in either destruction order
@@ -292,5 +323,10 @@ const void *rg_lds_blob_for(const rg_scene *s, const RgKernelArgs &a);
 uint32_t rg_host_tile_wlog(const rg_scene *s);
 // rg_capi.hip: free the host-visible paths' resources.
 void rg_image_res_release(rg_image_res &r);
+// rg_aa.hip: free the supersampled paths' resources.
+void rg_aa_res_release(rg_aa_res &r);
+// rg_capi.hip: ray counts summed over n band snapshots (4 words each), the first erroring
+// snapshot's status and pixel.
+rg_status rg_merge_band_snaps(const unsigned long long *snap, int n, rg_stats *total);
 
 #pragma GCC visibility pop

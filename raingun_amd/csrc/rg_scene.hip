@@ -81,6 +81,7 @@ void release(rg_scene *s) {
     s->frames.clear();
     rg_multi_release(s);
     rg_image_res_release(s->img);
+    rg_aa_res_release(s->aa);
     for (void *p : s->allocations) (void)hipFree(p);
     s->allocations.clear();
     if (s->lds_blob) (void)hipFree(s->lds_blob);

@@ -2,8 +2,10 @@
 // on the native host layer (libraingun_host.so: YAML scene, textures, PNG) and
 // the HIP renderer (libraingun_hip.so: rg_render_image).
 //
-//   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [-o FILE] [--gpu N] FILE
+//   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [-o FILE] [--gpu N] FILE
 //
+// --samples N (1..8, default 1; not in the reference): N x N rays per pixel on the
+// regular sub-pixel grid, box-filtered (rg_render_image_aa); --draft leaves it alone.
 // Flag semantics follow construct_app / RenderOptions::from (main.rs:21-96,
 // clap 2.23 overrides_with: the last of --4k/--hd wins; --draft forces
 // 800x600 and caps the recursion depth at 4, main.rs:74-75, 119-123, and
@@ -41,6 +43,7 @@ const char *kHelp =
     "        --gpu <N>              HIP device to render on (default 0).\n"
     "    -h, --height <PIXELS>      Height of output image.\n"
     "    -o, --output <FILENAME>    Specify filename of the rendered image.\n"
+    "        --samples <N>          Anti-aliasing: N x N rays per pixel, box-filtered (1..8, default 1).\n"
     "    -w, --width <PIXELS>       Width of output image.\n\n"
     "ARGS:\n"
     "    <FILE>    The scene definition file, in YAML format.\n";
@@ -58,12 +61,13 @@ const char *kHelp =
 
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
-    const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr;
+    const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr;
     int gpu = 0;
 };
 
 struct RenderOptions {  // render.rs:32-46
     uint32_t width = 800, height = 600;
+    uint32_t samples = 1;  // N x N rays per pixel (--samples)
     bool has_depth = false;
     uint32_t max_recursion_depth = 0;
 };
@@ -108,6 +112,7 @@ Args parse_args(int argc, char **argv) {
             else if (name == "height") a.height = take_value(i, "--height <PIXELS>", val);
             else if (name == "output") a.output = take_value(i, "--output <FILENAME>", val);
             else if (name == "gpu") a.gpu = std::atoi(take_value(i, "--gpu <N>", val));
+            else if (name == "samples") a.samples = take_value(i, "--samples <N>", val);
             else if (val) clap_error("Found argument '" + std::string(arg) + "' which wasn't expected, or isn't valid in this context");
             else if (name == "4k") { a.uhd = true; a.hd = false; }   // overrides_with("hd")
             else if (name == "hd") { a.hd = true; a.uhd = false; }   // overrides_with("4k")
@@ -133,6 +138,11 @@ Args parse_args(int argc, char **argv) {
 
 RenderOptions options_from(const Args &a) {  // main.rs:70-96
     RenderOptions o;
+    if (a.samples) {
+        if (!parse_u32(a.samples, &o.samples)) panic("Could not parse samples: ParseIntError { kind: InvalidDigit }");
+        if (o.samples < 1 || o.samples > 8)
+            clap_error(std::string("Invalid value for '--samples <N>': ") + a.samples + " is not between 1 and 8");
+    }
     if (a.draft) {
         o.has_depth = true;
         o.max_recursion_depth = 4;
@@ -199,7 +209,8 @@ int main(int argc, char **argv) {
     std::vector<uint8_t> rgba((size_t)opts.width * opts.height * 4);
 
     auto t0 = std::chrono::steady_clock::now();  // render.rs:54-56
-    st = rg_render_image(scene, opts.width, opts.height, rgba.data(), nullptr);
+    st = opts.samples > 1 ? rg_render_image_aa(scene, opts.width, opts.height, opts.samples, rgba.data(), nullptr, nullptr)
+                          : rg_render_image(scene, opts.width, opts.height, rgba.data(), nullptr);
     auto t1 = std::chrono::steady_clock::now();
     if (st != RG_OK) panic(rg_status_string(st));
     st = rgh_png_write(output.c_str(), rgba.data(), opts.width, opts.height);  // render.rs:58

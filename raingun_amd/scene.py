@@ -335,6 +335,39 @@ class DeviceScene:
                    "rg_render_image")
         return out
 
+    def render_image_aa(self, width: int, height: int, samples: int, want_rgb: bool = False,
+                        stats: Optional[_abi.rg_stats] = None, out: Optional[np.ndarray] = None):
+        """rg_render_image_aa: render_image with samples x samples rays per pixel on the regular
+        sub-pixel grid, box-filtered (raingun_amd/aa.py states the arithmetic).  Returns the
+        (height, width, 4) uint8 frame, or (frame, (height, width, 3) float32 means) with want_rgb."""
+        if out is None:
+            out = np.empty((height, width, 4), dtype=np.uint8)
+        assert out.shape == (height, width, 4) and out.dtype == np.uint8 and out.flags.c_contiguous
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        st = stats if stats is not None else _abi.rg_stats()
+        _abi.check(_abi.lib().rg_render_image_aa(self.handle, width, height, int(samples), out.ctypes.data,
+                                                 rgb.ctypes.data if rgb is not None else None, C.byref(st)),
+                   "rg_render_image_aa")
+        return (out, rgb) if want_rgb else out
+
+    def resolve_box(self, rgb: np.ndarray, samples: int):
+        """rg_resolve_box on this scene's device: (samples*H, samples*W, 3) float32 samples ->
+        ((H, W, 3) float32 means, (H, W, 4) uint8 RGBA), as aa.resolve_box computes them."""
+        k = int(samples)
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3 or k < 1 or rgb.shape[0] % k or rgb.shape[1] % k:
+            raise ValueError("expected (samples*height, samples*width, 3) float32 samples")
+        h, w = rgb.shape[0] // k, rgb.shape[1] // k
+        mean = np.empty((h, w, 3), dtype=np.float32)
+        rgba = np.empty((h, w, 4), dtype=np.uint8)
+        _abi.check(_abi.lib().rg_resolve_box(int(self.device), rgb.ctypes.data, w, h, k, rgba.ctypes.data,
+                                             mean.ctypes.data), "rg_resolve_box")
+        return mean, rgba
+
+    def set_aa_band_rows(self, rows: int) -> None:
+        """Output rows per band of supersampled renders (0: automatic; include/raingun_debug.h)."""
+        _abi.check(_abi.lib().rg_debug_set_aa_band_rows(self.handle, int(rows)))
+
     def render_multi(self, width: int, height: int, ngpus: int, tile_rows: int = 0,
                      stats: Optional[_abi.rg_stats] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
         """rg_render_multi: the frame over `ngpus` devices of this process (row
@@ -405,9 +438,12 @@ class Scene:                   # scene.rs:11-31
         return DeviceScene(self, device)
 
     # scene.rs:41-43 -> rendering::render_image (rendering.rs:24-38), on the GPU
-    def render_image(self, width: int, height: int, device: int = 0) -> np.ndarray:
+    # samples > 1: samples x samples rays per pixel, box-filtered (rg_render_image_aa)
+    def render_image(self, width: int, height: int, device: int = 0, samples: int = 1) -> np.ndarray:
         ds = DeviceScene(self, device)
         try:
+            if samples != 1:
+                return ds.render_image_aa(width, height, samples)
             return ds.render_image(width, height)
         finally:
             ds.close()
