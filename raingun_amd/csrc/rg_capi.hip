@@ -4,16 +4,18 @@
 // memory, the split of the two), streaming bands, host buffer registration,
 // the batch closest-hit query and the debug setters.  The scene is in
 // rg_scene.hip, the tiled launch every path here goes through in
-// rg_launch.hip, the pageable-frame copy pool in rg_copy_pool.cpp, the
-// single-process multi-GPU entry (rg_render_multi) in rg_multi.hip, the
-// supersampled frames (rg_render_image_aa) in rg_aa.hip.  No
-// exception or abort crosses the ABI.
+// rg_launch.hip, the streams, events and buffers of a banded frame, its
+// delivery to the caller and the stats tail of every path here in rg_bands.hip,
+// the band arithmetic in rg_band_plan.h, the pageable-frame copy pool in
+// rg_copy_pool.cpp, the single-process multi-GPU entry (rg_render_multi) in
+// rg_multi.hip, the supersampled frames (rg_render_image_aa) in rg_aa.hip.
+// Once a path here has enqueued work that stores into the caller's buffer,
+// every error exit drains its streams first (rg_bands_drain).  No exception or
+// abort crosses the ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <memory>
-#include <vector>
 
 #include "../../include/raingun.h"
 #include "../../include/raingun_debug.h"
@@ -28,20 +30,10 @@
 #endif
 
 void rg_image_res_release(rg_image_res &r) {
-    for (hipStream_t &st : r.rs)
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }
-    if (r.cs) { (void)hipStreamSynchronize(r.cs); (void)hipStreamDestroy(r.cs); r.cs = nullptr; }
-    for (hipEvent_t &e : r.ev_done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    for (hipEvent_t &e : r.ev_copy) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    for (hipEvent_t *e : {&r.ev_t0, &r.ev_t1, &r.ev_join})
-        if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-    if (r.d_rgba) (void)hipFree(r.d_rgba);
-    if (r.d_rgb) (void)hipFree(r.d_rgb);
-    if (r.h_stage) (void)hipHostFree(r.h_stage);
+    rg_bands_release(r);  // first: it waits for the streams
     if (r.h_frame) (void)hipHostFree(r.h_frame);
     if (r.h_flags) (void)hipHostFree(r.h_flags);
     if (r.h_cancel) (void)hipHostFree(r.h_cancel);
-    if (r.h_snap) (void)hipHostFree(r.h_snap);
     r = rg_image_res{};
 }
 
@@ -111,32 +103,14 @@ int32_t rg_device_count(void) {
 
 // ---------------------------------------------------------------- host-visible frames
 // The drop-in for rendering::render_image (rendering.rs:24-38) returns the
-// frame in HOST memory.  A 4K RGBA8 frame is 33 MB, about as long on PCIe
-// (~55 GB/s) as its render, so the frame is rendered in K row bands on two
-// render streams and band b's device-to-host copy (on a copy stream) runs
-// while bands b+1.. render.  A pinned caller buffer (hipHostMalloc'd, or
-// registered with rg_host_register) receives the DMA directly; a pageable
-// one is fed from a ring of pinned staging slots by host memcpy, overlapped
-// with the following bands' DMA.  Device framebuffer, staging, streams and
-// events belong to the scene and are reused across calls.
+// frame in HOST memory: rendered in row bands (rg_band_plan.h) and delivered
+// band by band (rg_bands.hip), or written over PCIe by the kernel itself.
+// Device framebuffer, staging, streams and events belong to the scene and are
+// reused across calls.
 namespace {
 
-// Bands of a banded host-visible frame: the first band's copy starts while
-// the later bands render (the frame's PCIe transfer alone: ~0.59 ms for 33 MB
-// at the measured 56 GB/s, profiles/r02/host_visible/d2h_probe.jsonl).  ~2 Mpx
-// per band, at most 3: a 4K frame in 3 bands 0.95 ms, in 16 bands 1.46 ms --
-// small launches leave most of the GPU idle (hv_sweep_bands_before.jsonl).
-int image_bands(const rg_scene *s, size_t px) {
-    if (s->image_bands > 0) return s->image_bands;
-    const size_t k = px / RG_IMAGE_BAND_PX;
-    return (int)std::max<size_t>(1, std::min<size_t>(3, k));
-}
-
-rg_status ensure_image_res(const rg_scene *s) {
-    rg_image_res &r = s->img;
-    if (r.cs) return RG_OK;
-    bool good = true;
-#if RG_IMAGE_STREAM_CUMASK
+// The scene's band resource set (rg_bands.h), for `bands` bands.
+rg_status ensure_image_res(const rg_scene *s, uint32_t bands) {
     // The host frame's two render streams run concurrently (split frames: the device part on
     // rs[0], the one-launch part on rs[1]), so they must not share a hardware queue.  HIP hands a
     // plain new stream one of the process's shared queues, and where it lands depends on the
@@ -145,30 +119,7 @@ rg_status ensure_image_res(const rg_scene *s) {
     // (profiles/r06/s32, s36).  A stream with a CU mask (every CU) gets a hardware queue of its
     // own: rs[1] is made so.  rs[0] stays a plain stream -- the heavy scenes' one-launch frame runs
     // there, and on a CU-masked queue it measured 2.32 instead of 2.03 ms in two of three runs (s37).
-    {
-        int cus = 0;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-        std::vector<uint32_t> mask((size_t)std::max(1, (cus + 31) / 32), 0xFFFFFFFFu);
-        if (cus % 32) mask.back() = (1u << (cus % 32)) - 1u;
-        good = good && ok(hipStreamCreateWithFlags(&r.rs[0], hipStreamNonBlocking)) &&
-               ok(hipExtStreamCreateWithCUMask(&r.rs[1], (uint32_t)mask.size(), mask.data()));
-    }
-#else
-    for (hipStream_t &st : r.rs) good = good && ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-#endif
-    good = good && ok(hipStreamCreateWithFlags(&r.cs, hipStreamNonBlocking));
-    for (hipEvent_t &e : r.ev_done) good = good && ok(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (hipEvent_t &e : r.ev_copy) good = good && ok(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    good = good && ok(hipEventCreate(&r.ev_t0)) && ok(hipEventCreate(&r.ev_t1)) &&
-           ok(hipEventCreateWithFlags(&r.ev_join, hipEventDisableTiming));
-    void *snap = nullptr;
-    good = good && ok(hipHostMalloc(&snap, RG_IMAGE_MAX_BANDS * 4 * sizeof(unsigned long long), hipHostMallocDefault));
-    r.h_snap = static_cast<unsigned long long *>(snap);
-    if (!good) {
-        rg_image_res_release(r);
-        return RG_ERR_DEVICE;
-    }
-    return RG_OK;
+    return rg_bands_ensure(s->img, s->device, bands, RG_IMAGE_STREAM_CUMASK != 0);
 }
 
 // Wait until tiles [t0, t1) of the launch carry `seq` (the kernel publishes a
@@ -218,31 +169,6 @@ host_grid host_tile_grid(uint32_t W, uint32_t rows, uint32_t wlog) {
     return {TH, tiles_x, tile_rows, tiles_x * tile_rows};
 }
 
-}  // namespace
-
-// Ray counts summed over n band snapshots (4 words each); the first erroring snapshot in index
-// order gives the status and the pixel (bands in row order: it holds the lowest erroring pixel).
-// Shared with rg_aa.hip.
-rg_status rg_merge_band_snaps(const unsigned long long *snap, int n, rg_stats *total) {
-    std::memset(total, 0, sizeof *total);
-    total->error_pixel = -1;
-    rg_status err = RG_OK;
-    for (int b = 0; b < n; ++b) {
-        rg_stats bs;
-        const rg_status e = rg_snap_status(snap + 4 * b, &bs);
-        total->rays.primary += bs.rays.primary;
-        total->rays.shadow += bs.rays.shadow;
-        total->rays.secondary += bs.rays.secondary;
-        if (e != RG_OK && err == RG_OK) {
-            err = e;
-            total->error_pixel = bs.error_pixel;
-        }
-    }
-    return err;
-}
-
-namespace {
-
 // Host-visible frame in ONE launch, no device framebuffer and no copy engine:
 // the kernel's pixel stores go straight over PCIe into page-locked host memory
 // (8x8-tile-shaped 4-B stores reach 52.7 GB/s of the 55.8 GB/s a DMA copy
@@ -280,31 +206,25 @@ rg_status render_host_direct(const rg_scene *s, uint32_t W, uint32_t H, const rg
     d.frame_seq = seq;
     d.tile_wlog = wl;
     d.host_frame = true;
+    // from here on the kernel may be storing into the caller's buffer: error exits drain
     st = rg_launch_tiles(s, d);
-    if (st != RG_OK) return st;
-    if (!ok(hipEventRecord(r.ev_t1, rs))) return RG_ERR_DEVICE;
+    if (st != RG_OK) return rg_bands_drain(r, st);
+    if (!ok(hipEventRecord(r.ev_t1, rs))) return rg_bands_drain(r, RG_ERR_DEVICE);
     if (pageable) {
-        if (!r.pool) r.pool = std::make_shared<rg_copy_pool>(RG_COPY_HELPERS);
-        rg_copy_pool::Active active(*r.pool);
+        rg_copy_pool &pool = rg_bands_pool(r);
+        rg_copy_pool::Active active(pool);
         // bands of whole tile rows, ~RG_IMAGE_BAND_PX / 4 pixels each (the queue hands out tiles in raster order)
         const size_t band_tr = std::max<size_t>(1, (RG_IMAGE_BAND_PX / 4) / ((size_t)W * TH));
         for (size_t tr0 = 0; tr0 < tile_rows && st == RG_OK; tr0 += band_tr) {
             const size_t tr1 = std::min(tile_rows, tr0 + band_tr);
             if ((st = wait_tiles(r.h_flags, tr0 * tiles_x, tr1 * tiles_x, seq, r.ev_t1)) != RG_OK) break;
             const size_t y0 = tr0 * TH, y1 = std::min<size_t>(rows, tr1 * TH);
-            r.pool->copy(rgba_out + y0 * row4, static_cast<uint8_t *>(r.h_frame) + y0 * row4, (y1 - y0) * row4);
+            pool.copy(rgba_out + y0 * row4, static_cast<uint8_t *>(r.h_frame) + y0 * row4, (y1 - y0) * row4);
         }
     }
-    if (!ok(hipStreamSynchronize(rs))) return RG_ERR_DEVICE;
+    if (!ok(hipStreamSynchronize(rs))) return rg_bands_drain(r, RG_ERR_DEVICE);
     if (st != RG_OK) return st;
-    rg_stats total;
-    std::memset(&total, 0, sizeof total);
-    const rg_status err = rg_snap_status(r.h_snap, &total);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, r.ev_t0, r.ev_t1);
-    total.kernel_ms = ms;
-    if (stats) *stats = total;
-    return err;
+    return rg_finish_stats(r.h_snap, 1, r.ev_t0, r.ev_t1, stats);
 }
 
 // Host-visible frame into a page-locked buffer, split in two concurrent parts
@@ -333,19 +253,11 @@ rg_status render_host_split(const rg_scene *s, uint32_t W, uint32_t H, const rg_
     const uint32_t ja = std::min(nt - 1u, std::max(1u, (uint32_t)(((unsigned long long)nt * (unsigned)pct + 50u) / 100u)));
     const size_t a_bytes = (size_t)ja * TR * row4;  // rows [0, ja TR): below H (ja < nt)
     if (rows > H) std::memset(rgba_out + (size_t)H * row4, 0, (size_t)(rows - H) * row4);  // the tiling's padding
-    rg_status st = rg_grow(RG_MEM_DEVICE, r.d_rgba, r.d_rgba_cap, a_bytes + 4);
+    rg_status st = rg_bands_ensure_frame(r, (size_t)ja * TR * W, false);
     if (st != RG_OK) return st;
-    if (!ok(hipEventRecord(r.ev_t0, r.rs[0])) || !ok(hipStreamWaitEvent(r.rs[1], r.ev_t0, 0))) return RG_ERR_DEVICE;
+    if (!rg_bands_fork(r)) return RG_ERR_DEVICE;
     // Once either part is enqueued, every exit first drains both render streams and the copy
-    // stream: part B's kernel and part A's DMA store into the caller's buffer, which the caller
-    // owns again when this call returns (rendering.rs:24-38 returns a finished ImageBuffer).
-    auto drain = [&](rg_status e) -> rg_status {
-        (void)hipStreamSynchronize(r.rs[1]);
-        (void)hipStreamSynchronize(r.rs[0]);
-        (void)hipStreamSynchronize(r.cs);
-        (void)hipGetLastError();
-        return e;
-    };
+    // stream: part B's kernel and part A's DMA store into the caller's buffer.
     // part A (device memory): tiles [0, ja) of the frame
     auto launch_a = [&]() -> rg_status {
         if (s->split_fail_a > 0) {  // rg_debug_fail_split_a: this launch reports failure without running
@@ -369,22 +281,16 @@ rg_status render_host_split(const rg_scene *s, uint32_t W, uint32_t H, const rg_
     };
     // part B's persistent host-frame launch first, part A's beside it: B's PCIe writes start at once
     // (test1 4K pinned 0.854 -> 0.80 ms at 35 %; 30 % 0.83, 40 % 0.91: profiles/r05/s32)
-    if ((st = launch_b()) != RG_OK || (st = launch_a()) != RG_OK) return drain(st);
+    if ((st = launch_b()) != RG_OK || (st = launch_a()) != RG_OK) return rg_bands_drain(r, st);
     if (!ok(hipStreamWaitEvent(r.cs, r.ev_done[0], 0)) ||
         !ok(hipMemcpyAsync(rgba_out, r.d_rgba, a_bytes, hipMemcpyDeviceToHost, r.cs)) ||
         !ok(hipEventRecord(r.ev_copy[0], r.cs)) || !ok(hipStreamWaitEvent(r.rs[1], r.ev_copy[0], 0)) ||
         !ok(hipEventRecord(r.ev_t1, r.rs[1])))
-        return drain(RG_ERR_DEVICE);
+        return rg_bands_drain(r, RG_ERR_DEVICE);
     const bool synced1 = ok(hipStreamSynchronize(r.rs[1]));
     const bool synced0 = ok(hipStreamSynchronize(r.rs[0]));
-    if (!synced1 || !synced0) return drain(RG_ERR_DEVICE);
-    rg_stats total;
-    const rg_status err = rg_merge_band_snaps(r.h_snap, 2, &total);  // part A holds the lower pixel indices: its error first
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, r.ev_t0, r.ev_t1);
-    total.kernel_ms = ms;
-    if (stats) *stats = total;
-    return err;
+    if (!synced1 || !synced0) return rg_bands_drain(r, RG_ERR_DEVICE);
+    return rg_finish_stats(r.h_snap, 2, r.ev_t0, r.ev_t1, stats);  // part A holds the lower pixel indices: its error first
 }
 
 }  // namespace
@@ -397,7 +303,11 @@ rg_status rg_render_host(const rg_scene *s, uint32_t W, uint32_t H, const rg_til
     if ((unsigned long long)rows * W >= (1ull << 32) || (unsigned long long)H * W >= (1ull << 32))
         return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
-    rg_status st = ensure_image_res(s);
+    // A whole-frame tiling (stride 1) is re-cut into K bands of BR rows (tiling {BR, K, b}
+    // renders exactly rows [b BR, (b+1) BR)); a sharded tiling is rendered in one launch.
+    const bool banded = t->tile_stride == 1;
+    const rg_band_plan p = banded ? rg_image_band_plan(s->image_bands, W, H, RG_IMAGE_BAND_PX) : rg_one_band(W, rows);
+    rg_status st = ensure_image_res(s, std::max(p.bands, 2u));  // the split frame has two parts
     if (st != RG_OK) return st;
     rg_image_res &r = s->img;
     // Path choice (4K frames): into page-locked buffers one launch writing host
@@ -418,97 +328,28 @@ rg_status rg_render_host(const rg_scene *s, uint32_t W, uint32_t H, const rg_til
         if (direct) return render_host_direct(s, W, H, t, rows, rgba_out, stats);
     }
 
-    // Bands.  A whole-frame tiling (stride 1) is re-cut into K bands of BR
-    // rows (tiling {BR, K, b} renders exactly rows [b BR, (b+1) BR)); a sharded
-    // tiling is rendered in one launch.
-    const bool banded = t->tile_stride == 1;
-    int K = 1;
-    uint32_t BR = rows;
-    if (banded) {
-        K = image_bands(s, (size_t)H * W);
-        BR = (H + (uint32_t)K - 1) / (uint32_t)K;
-        BR = (BR + 7u) & ~7u;  // whole 8x8 tiles per band
-        K = (int)((H + BR - 1) / BR);
-    }
-    const uint32_t dev_rows = banded ? (uint32_t)K * BR : rows;
     const bool want_rgb = rgb_out != nullptr;
     const size_t row4 = (size_t)W * 4, row12 = (size_t)W * 12;
-    if ((st = rg_grow(RG_MEM_DEVICE, r.d_rgba, r.d_rgba_cap, (size_t)dev_rows * row4 + 4)) != RG_OK) return st;
-    if (want_rgb && (st = rg_grow(RG_MEM_DEVICE, r.d_rgb, r.d_rgb_cap, (size_t)dev_rows * row12 + 4)) != RG_OK) return st;
-    const bool direct = rg_host_is_pinned(rgba_out, (size_t)rows * row4) &&
-                        (!want_rgb || rg_host_is_pinned(rgb_out, (size_t)rows * row12));
-    const int R = RG_IMAGE_STAGE_SLOTS;
-    const size_t slot_bytes = (size_t)BR * (row4 + (want_rgb ? row12 : 0));
-    if (!direct && (st = rg_grow(RG_MEM_PINNED, r.h_stage, r.h_stage_cap, (size_t)R * slot_bytes)) != RG_OK) return st;
-    // host rows of band b: [b BR, min(H, (b+1) BR)) when banded, else all `rows`
-    auto host_rows = [&](int b) -> uint32_t {
-        if (!banded) return rows;
-        const uint32_t r0 = (uint32_t)b * BR;
-        return std::min(H, r0 + BR) - r0;
-    };
-    auto stage_rgba = [&](int b) { return static_cast<uint8_t *>(r.h_stage) + (size_t)(b % R) * slot_bytes; };
-    auto stage_rgb = [&](int b) { return reinterpret_cast<float *>(stage_rgba(b) + (size_t)BR * row4); };
-
-    if (!ok(hipEventRecord(r.ev_t0, r.rs[0])) || !ok(hipStreamWaitEvent(r.rs[1], r.ev_t0, 0))) return RG_ERR_DEVICE;
-    for (int b = 0; b < K; ++b) {
+    if ((st = rg_bands_ensure_frame(r, (size_t)p.bands * p.band_rows * W, want_rgb)) != RG_OK) return st;
+    uint8_t *d_rgba = static_cast<uint8_t *>(r.d_rgba);
+    float *d_rgb = want_rgb ? static_cast<float *>(r.d_rgb) : nullptr;
+    if (!rg_bands_fork(r)) return RG_ERR_DEVICE;
+    for (uint32_t b = 0; b < p.bands; ++b) {
         hipStream_t rs = r.rs[b & 1];
-        rg_tiling bt = banded ? rg_tiling{BR, (uint32_t)K, (uint32_t)b} : *t;
-        const size_t off = banded ? (size_t)b * BR : 0;
-        rg_launch_desc d = frame_launch(W, H, bt, static_cast<uint8_t *>(r.d_rgba) + off * row4, rs, r.h_snap + 4 * b);
-        if (want_rgb) d.rgb = reinterpret_cast<float *>(static_cast<uint8_t *>(r.d_rgb) + off * row12);
-        st = rg_launch_tiles(s, d);
-        if (st != RG_OK) return st;
-        if (!ok(hipEventRecord(r.ev_done[b], rs))) return RG_ERR_DEVICE;
+        const rg_tiling bt = banded ? rg_tiling{p.band_rows, p.bands, b} : *t;
+        const size_t off = (size_t)b * p.band_rows * W;
+        rg_launch_desc d = frame_launch(W, H, bt, d_rgba + off * 4, rs, r.h_snap + 4 * b);
+        if (want_rgb) d.rgb = d_rgb + off * 3;
+        if ((st = rg_launch_tiles(s, d)) != RG_OK) return rg_bands_drain(r, st);
+        if (!ok(hipEventRecord(r.ev_done[b], rs))) return rg_bands_drain(r, RG_ERR_DEVICE);
     }
-    if (!ok(hipEventRecord(r.ev_join, r.rs[1])) || !ok(hipStreamWaitEvent(r.rs[0], r.ev_join, 0)) ||
-        !ok(hipEventRecord(r.ev_t1, r.rs[0])))
-        return RG_ERR_DEVICE;
-    auto enqueue_copy = [&](int b) -> bool {
-        const size_t off = banded ? (size_t)b * BR : 0;
-        const uint32_t n = host_rows(b);
-        uint8_t *dst4 = direct ? rgba_out + off * row4 : stage_rgba(b);
-        float *dst12 = want_rgb ? (direct ? rgb_out + off * (size_t)W * 3 : stage_rgb(b)) : nullptr;
-        if (!ok(hipStreamWaitEvent(r.cs, r.ev_done[b], 0))) return false;
-        if (n > 0 && !ok(hipMemcpyAsync(dst4, static_cast<uint8_t *>(r.d_rgba) + off * row4, (size_t)n * row4,
-                                        hipMemcpyDeviceToHost, r.cs)))
-            return false;
-        if (n > 0 && dst12 && !ok(hipMemcpyAsync(dst12, static_cast<uint8_t *>(r.d_rgb) + off * row12,
-                                                 (size_t)n * row12, hipMemcpyDeviceToHost, r.cs)))
-            return false;
-        return ok(hipEventRecord(r.ev_copy[b], r.cs));
-    };
-    if (direct) {
-        for (int b = 0; b < K; ++b)
-            if (!enqueue_copy(b)) return RG_ERR_DEVICE;
-        if (!ok(hipStreamSynchronize(r.cs))) return RG_ERR_DEVICE;
-    } else {
-        // pageable destination: DMA into the pinned staging ring, then a
-        // parallel host copy of each band while the next bands' DMA runs
-        if (!r.pool) r.pool = std::make_shared<rg_copy_pool>(RG_COPY_HELPERS);
-        rg_copy_pool::Active active(*r.pool);
-        for (int b = 0; b < std::min(K, R); ++b)
-            if (!enqueue_copy(b)) return RG_ERR_DEVICE;
-        for (int b = 0; b < K; ++b) {
-            if (!ok(hipEventSynchronize(r.ev_copy[b]))) return RG_ERR_DEVICE;
-            const size_t off = banded ? (size_t)b * BR : 0;
-            const uint32_t n = host_rows(b);
-            r.pool->copy(rgba_out + off * row4, stage_rgba(b), (size_t)n * row4);
-            if (want_rgb) r.pool->copy(rgb_out + off * (size_t)W * 3, stage_rgb(b), (size_t)n * row12);
-            if (b + R < K && !enqueue_copy(b + R)) return RG_ERR_DEVICE;
-        }
-    }
-    if (!ok(hipStreamSynchronize(r.rs[0])) || !ok(hipStreamSynchronize(r.rs[1]))) return RG_ERR_DEVICE;
+    if (!rg_bands_join(r)) return rg_bands_drain(r, RG_ERR_DEVICE);
+    if ((st = rg_bands_deliver(r, p, d_rgba, d_rgb, rgba_out, rgb_out)) != RG_OK) return st;
     if (banded && rows > H) {  // padding rows of a whole-frame tiling whose tile_rows does not divide H
         std::memset(rgba_out + (size_t)H * row4, 0, (size_t)(rows - H) * row4);
         if (want_rgb) std::memset(rgb_out + (size_t)H * W * 3, 0, (size_t)(rows - H) * row12);
     }
-    rg_stats total;
-    const rg_status err = rg_merge_band_snaps(r.h_snap, K, &total);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, r.ev_t0, r.ev_t1);
-    total.kernel_ms = ms;
-    if (stats) *stats = total;
-    return err;
+    return rg_finish_stats(r.h_snap, (int)p.bands, r.ev_t0, r.ev_t1, stats);
 }
 
 extern "C" {
@@ -557,7 +398,7 @@ rg_status rg_render_stream(const rg_scene *s, uint32_t width, uint32_t height, u
     if (width < height) return RG_ERR_PORTRAIT;
     if ((unsigned long long)height * width >= (1ull << 32)) return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
-    rg_status st = ensure_image_res(s);
+    rg_status st = ensure_image_res(s, 1);
     if (st != RG_OK) return st;
     rg_image_res &r = s->img;
     const size_t row4 = (size_t)width * 4, bytes = (size_t)height * row4;
@@ -585,9 +426,10 @@ rg_status rg_render_stream(const rg_scene *s, uint32_t width, uint32_t height, u
     d.cancel = cancel_dev;
     d.tile_wlog = wl;
     d.host_frame = true;
+    // from here on error exits drain: the callback's bands are read from a frame the kernel writes
     st = rg_launch_tiles(s, d);
-    if (st != RG_OK) return st;
-    if (!ok(hipEventRecord(r.ev_t1, rs))) return RG_ERR_DEVICE;
+    if (st != RG_OK) return rg_bands_drain(r, st);
+    if (!ok(hipEventRecord(r.ev_t1, rs))) return rg_bands_drain(r, RG_ERR_DEVICE);
     const uint8_t *frame = static_cast<const uint8_t *>(r.h_frame);
     for (uint32_t y0 = 0; y0 < height; y0 += tile_rows) {
         const uint32_t n = std::min(tile_rows, height - y0);
@@ -600,14 +442,8 @@ rg_status rg_render_stream(const rg_scene *s, uint32_t width, uint32_t height, u
             break;
         }
     }
-    if (!ok(hipStreamSynchronize(rs))) return RG_ERR_DEVICE;
-    rg_stats total;
-    std::memset(&total, 0, sizeof total);
-    const rg_status err = rg_snap_status(r.h_snap, &total);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, r.ev_t0, r.ev_t1);
-    total.kernel_ms = ms;
-    if (stats) *stats = total;
+    if (!ok(hipStreamSynchronize(rs))) return rg_bands_drain(r, RG_ERR_DEVICE);
+    const rg_status err = rg_finish_stats(r.h_snap, 1, r.ev_t0, r.ev_t1, stats);
     if (st == RG_OK && err != RG_OK) return err;
     return st;
 }

@@ -1,8 +1,10 @@
 // rg_internal.h — host-side state behind the opaque rg_scene handle, shared
 // by rg_scene.hip (scene upload, kernel arguments), rg_launch.hip (per-stream
 // launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
-// streaming, debug setters), rg_frames.hip (frames in flight over N processes)
-// and rg_multi.hip (one process driving N devices).  Not part of the ABI.
+// streaming, debug setters), rg_aa.hip (supersampled frames), rg_frames.hip
+// (frames in flight over N processes) and rg_multi.hip (one process driving N
+// devices).  The band resource set the two kinds of host frames are built on is
+// in rg_bands.h, the band arithmetic in rg_band_plan.h.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +15,7 @@
 
 #include "../../include/raingun.h"
 #include "../../include/raingun_debug.h"
+#include "rg_bands.h"
 #include "rg_copy_pool.h"
 #include "rg_device.h"
 #include "rg_lightbuf_ray.h"
@@ -64,9 +67,6 @@ struct rg_launch_ctx {
 #ifndef RG_IMAGE_STREAM_CUMASK
 #define RG_IMAGE_STREAM_CUMASK 1  // host-frame render streams with a CU mask: a hardware queue each (rg_capi.hip)
 #endif
-#define RG_IMAGE_STAGE_SLOTS 4  // pinned staging slots of the host-visible image path
-#define RG_IMAGE_MAX_BANDS 16   // events / counter snapshots per host-visible render or stream ring
-#define RG_IMAGE_BAND_PX (2u << 20)    // ~pixels per band of a banded host-visible frame
 #ifndef RG_HOST_TILE_WLOG_LIGHT
 // one-launch host-visible frames of light-path scenes: 64x1 tiles, so that a wave's ring of
 // consecutive tiles (rg_kernels.hip RG_HOST_RING) is one contiguous run of host memory
@@ -80,56 +80,28 @@ struct rg_launch_ctx {
 #define RG_HOST_TILE_WLOG 4
 #endif
 // Resources of the host-visible paths (rg_render_image / rg_render_tiles /
-// rg_render_stream), owned by the scene and reused across calls.
-struct rg_image_res {
-    std::shared_ptr<rg_copy_pool> pool;      // pageable destinations (created on first use)
-    hipStream_t rs[2] = {nullptr, nullptr};  // render streams (bands alternate)
-    hipStream_t cs = nullptr;                // device-to-host copies
-    hipEvent_t ev_done[RG_IMAGE_MAX_BANDS] = {};
-    hipEvent_t ev_copy[RG_IMAGE_MAX_BANDS] = {};
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_join = nullptr;
-    void *d_rgba = nullptr;
-    size_t d_rgba_cap = 0;
-    void *d_rgb = nullptr;
-    size_t d_rgb_cap = 0;
-    void *h_stage = nullptr;  // pinned
-    size_t h_stage_cap = 0;
+// rg_render_stream), owned by the scene and reused across calls: a band resource set
+// (rg_bands.h) whose rs[1] has a hardware queue of its own, and what the one-launch
+// paths need.
+struct rg_image_res : rg_band_res {
     void *h_frame = nullptr;  // pinned, coherent: whole frames the kernel writes over PCIe (pageable destinations)
     size_t h_frame_cap = 0;
     uint32_t *h_flags = nullptr;  // pinned, coherent: per-tile publication words (RgKernelArgs::tile_flags)
     size_t h_flags_cap = 0;       // bytes
     uint32_t seq = 0;             // frame sequence number the flags carry
     uint32_t *h_cancel = nullptr; // pinned, coherent: streaming cancellation word (RgKernelArgs::cancel)
-    unsigned long long *h_snap = nullptr;  // pinned: 4 counter words per band
 };
 
-#ifndef RG_AA_SLOT_BYTES
-// supersampled frames (rg_aa.hip): the scratch of one band of samples (RGBA8 + f32 RGB,
-// 16 B per sample) stays within this; two such slots, one per render stream
-#define RG_AA_SLOT_BYTES ((size_t)64 << 20)
-#endif
-#define RG_AA_MIN_BAND_ROWS 8   // output rows per band at least (automatic choice)
-#define RG_AA_MAX_SAMPLES 8     // samples per pixel side
+#define RG_AA_MAX_SAMPLES 8  // samples per pixel side
 // Resources of the supersampled paths (rg_render_image_aa / rg_render_aa_async), owned by
-// the scene and reused across calls.
-struct rg_aa_res {
-    std::shared_ptr<rg_copy_pool> pool;      // pageable destinations (created on first use)
-    hipStream_t rs[2] = {nullptr, nullptr};  // render + resolve streams (bands alternate)
-    hipStream_t cs = nullptr;                // device-to-host copies
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_join = nullptr, ev_fork = nullptr;
-    std::vector<hipEvent_t> ev_done, ev_copy;  // per band: resolved, copied
+// the scene and reused across calls: a band resource set of plain streams (render + resolve
+// on rs, d_rgba / d_rgb the resolved frame of the host entry), and the sample scratch.
+struct rg_aa_res : rg_band_res {
+    hipEvent_t ev_fork = nullptr;  // rg_render_aa_async: the caller's stream
     // per render stream, one band of samples: RGBA8 (the render kernel always writes it) and f32 RGB
     void *slot_rgba[2] = {nullptr, nullptr};
     void *slot_rgb[2] = {nullptr, nullptr};
     size_t slot_cap[2] = {0, 0};  // samples
-    void *d_rgba = nullptr;       // the resolved frame of the host entry
-    size_t d_rgba_cap = 0;
-    void *d_rgb = nullptr;
-    size_t d_rgb_cap = 0;
-    void *h_stage = nullptr;  // pinned staging ring (pageable destinations)
-    size_t h_stage_cap = 0;
-    unsigned long long *h_snap = nullptr;  // pinned: 4 counter words per band
-    size_t h_snap_cap = 0;                 // bytes
 };
 
 // Everything rg_scene_create uploads, as host tables (kept for replicas on
@@ -325,8 +297,5 @@ uint32_t rg_host_tile_wlog(const rg_scene *s);
 void rg_image_res_release(rg_image_res &r);
 // rg_aa.hip: free the supersampled paths' resources.
 void rg_aa_res_release(rg_aa_res &r);
-// rg_capi.hip: ray counts summed over n band snapshots (4 words each), the first erroring
-// snapshot's status and pixel.
-rg_status rg_merge_band_snaps(const unsigned long long *snap, int n, rg_stats *total);
 
 #pragma GCC visibility pop

@@ -532,14 +532,13 @@ rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
     if (!ok(hipEventRecord(m->ev1, m->streams[0]))) return RG_ERR_DEVICE;
     if (pageable) {
         // band b's image rows [b J n T, (b + 1) J n T) are complete once every device copied its part
-        rg_image_res &img = s->img;
-        if (!img.pool) img.pool = std::make_shared<rg_copy_pool>(RG_COPY_HELPERS);
-        rg_copy_pool::Active active(*img.pool);
+        rg_copy_pool &pool = rg_bands_pool(s->img);
+        rg_copy_pool::Active active(pool);
         for (int b = 0; b < K; ++b) {
             for (int i = 0; i < n; ++i)
                 if (!ok(hipSetDevice(m->devs[i])) || !ok(hipEventSynchronize(m->ev_copy[i][b]))) return RG_ERR_DEVICE;
             const size_t y0 = std::min<size_t>(H, (size_t)b * J * n * T), y1 = std::min<size_t>(H, (size_t)(b + 1) * J * n * T);
-            if (y1 > y0) img.pool->copy(rgba_out + y0 * row4, dst + y0 * row4, (y1 - y0) * row4);
+            if (y1 > y0) pool.copy(rgba_out + y0 * row4, dst + y0 * row4, (y1 - y0) * row4);
         }
     }
     for (int i = n - 1; i >= 0; --i) {

@@ -221,6 +221,52 @@ def test_render_tiles_rgb_host(oracle_lib, example_scenes, tile_rows, stride, of
     assert float(np.abs(rgb - o_rgb).max()) <= RGB_TOL
 
 
+def test_banded_and_supersampled_frames_interleaved(oracle_lib, example_scenes):
+    """Host-visible and supersampled frames of one scene in turn, into pageable memory: each kind
+    has band resources of its own (streams, events, device frame, staging ring), grown on demand
+    -- 1, then 16 bands of 8 rows (more than staging slots), then fewer again; supersampled bands
+    of 7 rows between them; then both at other sizes, with the f32 output.  Every frame equals the
+    CPU restatement's byte for byte (supersampled: the restatement at k w x k h, box-filtered in
+    numpy), ray counts equal."""
+    from raingun_amd import aa
+
+    scene = example_scenes["test1"]
+
+    def image(ds, w, h, bands):
+        o_st, o_rgba, _, o_counts, _ = _oracle(oracle_lib, scene, w, h)
+        assert o_st == 0
+        for k in bands:
+            ds.set_image_bands(k)
+            st = _abi.rg_stats()
+            got = ds.render_image(w, h, stats=st, out=np.full((h, w, 4), 123, dtype=np.uint8))
+            assert np.array_equal(got, o_rgba), f"{w}x{h}, {k} bands"
+            assert st.rays.as_dict() == o_counts, f"{w}x{h}, {k} bands"
+            assert st.error_pixel == -1
+
+    def supersampled(ds, w, h, k, band_rows, want_rgb):
+        o_st, _, o_rgb, o_counts, _ = _oracle(oracle_lib, scene, k * w, k * h)
+        assert o_st == 0
+        want_mean, want_rgba = aa.resolve_box(o_rgb, k)
+        ds.set_aa_band_rows(band_rows)
+        st = _abi.rg_stats()
+        got = ds.render_image_aa(w, h, k, want_rgb=want_rgb, stats=st)
+        rgba, mean = got if want_rgb else (got, None)
+        assert np.array_equal(rgba, want_rgba), f"{w}x{h} k {k}"
+        if want_rgb:
+            assert float(np.abs(mean.astype(np.float64) - want_mean.astype(np.float64)).max()) <= RGB_TOL
+        assert st.rays.as_dict() == o_counts, f"{w}x{h} k {k}"
+        assert st.error_pixel == -1
+
+    ds = DeviceScene(scene)
+    try:
+        image(ds, 160, 128, (1, 16, 3))
+        supersampled(ds, 64, 40, 2, 7, False)  # 6 bands
+        image(ds, 97, 61, (7,))                # 4 bands of 16 rows, the last one short
+        supersampled(ds, 101, 75, 3, 16, True)
+    finally:
+        ds.close()
+
+
 # ---------------------------------------------------------------- streaming
 @pytest.mark.parametrize("tile_rows", [32, 37, 240, 1])
 def test_stream_bands_match_oracle(oracle_lib, example_scenes, tile_rows):
