@@ -1,5 +1,5 @@
 // rg_bvh_ray.h — the f32 ray/box slab test of the BVH traversal, shared by the
-// kernel (rg_kernels.hip) and the CPU simulation test (tests/native/bvh_sim.cpp)
+// kernel (rg_k_bvh.h) and the CPU simulation test (tests/native/bvh_sim.cpp)
 // so the host check exercises the very expressions the GPU runs.
 //
 // Conservativeness (rg_bvh.cpp header): for a ray with |o_k| <= bvh_obound and

@@ -35,7 +35,7 @@ template <class T>
 __device__ __forceinline__ const RG_CONST T *rg_cptr(const T *p) { return (const RG_CONST T *)p; }
 
 struct alignas(16) RgSph { double cx, cy, cz, r2; };
-// f32 pre-filter records (see rg_kernels.hip, "f32 pre-filter"): conservative
+// f32 pre-filter records (see rg_k_intersect.h, "f32 pre-filter"): conservative
 // bounds, never values the exact test uses.
 struct alignas(16) RgSphF { float cx, cy, cz, r2hi; };       // c rounded to f32; r2 rounded up (+slack)
 struct alignas(16) RgSphF2 { float cchi, thrp, cc32; int32_t id; };  // |c|^2 rounded up; primary-ray threshold; fl32(c.c); YAML body id (= sph_id)
@@ -45,7 +45,7 @@ struct alignas(16) RgBox { double lo[3], hi[3]; };
 
 // 4-wide BVH over the sphere table (built on the host, rg_bvh.cpp).  Child
 // boxes are f32, inflated and rounded outward so that the f32 slab test can
-// only err towards "visit" (derivation: rg_kernels.hip, "BVH traversal").
+// only err towards "visit" (derivation: rg_k_bvh.h, "BVH traversal").
 // child[k] >= 0: internal node; child[k] < 0: leaf, v = ~child[k], spheres
 // [v >> 3, (v >> 3) + (v & 7) + 1) of the (BVH-ordered) sphere tables.
 struct alignas(16) RgBvhNode {
@@ -55,7 +55,7 @@ struct alignas(16) RgBvhNode {
     int32_t pad[3];
 };
 
-// Per-lane traversal (incoherent rays, rg_kernels.hip "bvh_lane") walks the
+// Per-lane traversal (incoherent rays, rg_k_bvh.h "bvh_lane") walks the
 // same 4-wide nodes with a per-lane stack in LDS.  Stack entry: the f32 bits
 // of the child's entry distance with the low RG_LANE_NODE_BITS cleared (a
 // lower bound, so pruning at pop is conservative) | the child's node index.
@@ -150,7 +150,7 @@ struct RgKernelArgs {
     const uint32_t *tile_perm;     // nullable: dequeue order of the 8x8 tiles (expensive first)
     unsigned long long *counters;  // [0]=primary [1]=shadow [2]=secondary [3]=~error key [16+16q]=tile queue heads (RG_COUNTER_WORDS words)
     unsigned long long *counters_next;  // nullable: the other counter set of the launch context, zeroed by the render kernel
-    // frames of the shading tree for depths above the compiled arrays (rg_kernels.hip FrameStack<0>)
+    // frames of the shading tree for depths above the compiled arrays (rg_k_frames.h FrameStack<0>)
     void *deep_stack;        // grid threads x (max_depth - 1) frames, frame i of thread g at [i * deep_stride + g]
     uint32_t deep_stride;    // threads of the grid the buffer was sized for
     int32_t nan_scene;       // a body or light parameter is non-finite or >= 1e100: NaN distances possible
@@ -217,11 +217,11 @@ __host__ __device__ inline unsigned long long rg_tile_count(const RgKernelArgs &
     return (unsigned long long)rg_tiles_x(a) * rg_tiles_y(a);
 }
 
-// sizeof(Frame) in rg_kernels.hip (the deep frame buffer is sized on the host)
+// sizeof(Frame) in rg_k_frames.h (the deep frame buffer is sized on the host)
 #define RG_FRAME_BYTES 88
 
 // Light-path frames into page-locked host memory (the one-launch host-frame kernels' LDS tile ring,
-// rg_kernels.hip): finished tiles per ring flush and consecutive tiles per queue slot, for launches
+// rg_render_kernel.h): finished tiles per ring flush and consecutive tiles per queue slot, for launches
 // below RG_RING_BIG_TILES 64-pixel tiles (rg_render_multi's device shares: balance over the waves)
 // and from it (whole frames, part B of split frames: long runs of host memory per flush).  test1 4K
 // (profiles/r06/s5/hv_ring_sweep.out): 8-device rehearsal 0.2895 ms banded -> 0.207 ms one launch

@@ -55,7 +55,7 @@ struct rg_launch_ctx {
     };
     bool perm_valid = false;
     PermKey perm_key{};
-    void *deep = nullptr;  // frames for depths above the compiled arrays (rg_kernels.hip FrameStack<0>)
+    void *deep = nullptr;  // frames for depths above the compiled arrays (rg_k_frames.h FrameStack<0>)
     size_t deep_bytes = 0;
     double *prim = nullptr;  // sensor x per column then sensor y per row (RgKernelArgs::prim_sx / prim_sy)
     size_t prim_cap = 0;     // bytes
@@ -69,7 +69,7 @@ struct rg_launch_ctx {
 #endif
 #ifndef RG_HOST_TILE_WLOG_LIGHT
 // one-launch host-visible frames of light-path scenes: 64x1 tiles, so that a wave's ring of
-// consecutive tiles (rg_kernels.hip RG_HOST_RING) is one contiguous run of host memory
+// consecutive tiles (rg_render_kernel.h RG_HOST_RING) is one contiguous run of host memory
 #define RG_HOST_TILE_WLOG_LIGHT 6
 #endif
 #ifndef RG_HOST_TILE_WLOG
@@ -134,7 +134,7 @@ struct rg_scene {
     float def[3] = {0, 0, 0};
     uint32_t max_depth = 10;
     int32_t n_sph = 0, n_pln = 0, n_dsk = 0, n_box = 0, n_bodies = 0, n_lights = 0, n_textures = 0;
-    bool nan_scene = false;  // NaN distances possible (rg_kernels.hip ray_exotic)
+    bool nan_scene = false;  // NaN distances possible (rg_k_trace.h ray_exotic)
     std::vector<void *> allocations;
     RgSph *sph = nullptr;
     double *sph_cc = nullptr;
@@ -163,7 +163,7 @@ struct rg_scene {
     float bvh_obound = 0.0f;
     double bvh_rbound = 0.0, bvh_margin = 0.0, bvh_extent = 0.0;
     rg_bvh_info bvh_info{};
-    int tile_order = -1;  // expensive tiles first (rg_kernels.hip "tile ordering"): -1 auto (heavy path), 0, 1
+    int tile_order = -1;  // expensive tiles first (rg_tile_order.hip "tile ordering"): -1 auto (heavy path), 0, 1
     int image_bands = 0;  // host-visible frames: 0 auto, -1 one launch writing host memory, -2 split, 1..16 row bands
     int host_split_pct = 0;  // -2 (split): percent of the frame's rows rendered into device memory + DMA (0: default)
     mutable int split_fail_a = 0;  // debug: the next N split renders report part A's launch as failed (rg_debug_fail_split_a)

@@ -1,0 +1,92 @@
+// rg_k_math.h — device vector and colour maths, the Rust casts, region counters and error reports
+// (the render kernels' headers, rg_k_*.h: see rg_render_kernel.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "rg_device.h"
+
+#pragma clang fp contract(off)
+
+namespace rgk {
+
+constexpr double SHADOW_BIAS = 1e-13;                 // lib.rs:11
+constexpr float PI_F = 3.14159265358979323846f;       // std::f32::consts::PI
+
+// MODE_WAIT: the lane's top frame awaits a subtree another lane is tracing (task splitting)
+enum : int { MODE_CLOSEST = 0, MODE_SHADOW = 1, MODE_DONE = 2, MODE_WAIT = 3, MODE_SHADOW_H = 4 };
+// MODE_SHADOW_H: an idle lane tracing one shadow ray for another lane of its wave (shadow fan-out)
+// FR_REFR_TASK / FR_REFR_WAIT carry their pool slot in bits 8+ of Frame::type
+enum : int { FR_REFL = 0, FR_REFR_T = 1, FR_REFR_R = 2, FR_REFR_TASK = 4, FR_REFR_WAIT = 5 };
+
+struct V3 { double x, y, z; };
+struct C3 { float r, g, b; };
+
+__device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
+__device__ __forceinline__ V3 add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ V3 sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ V3 scl(V3 a, double s) { return v3(a.x * s, a.y * s, a.z * s); }
+__device__ __forceinline__ V3 neg(V3 a) { return v3(-a.x, -a.y, -a.z); }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ V3 normalize(V3 a) { return scl(a, 1.0 / sqrt(dot(a, a))); }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) {
+    return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+
+__device__ __forceinline__ C3 c3(float r, float g, float b) { return C3{r, g, b}; }
+__device__ __forceinline__ C3 cadd(C3 a, C3 b) { return c3(a.r + b.r, a.g + b.g, a.b + b.b); }
+__device__ __forceinline__ C3 cmul(C3 a, C3 b) { return c3(a.r * b.r, a.g * b.g, a.b * b.b); }
+__device__ __forceinline__ C3 cscl(C3 a, float s) { return c3(a.r * s, a.g * s, a.b * s); }
+__device__ __forceinline__ C3 cclamp(C3 a) {  // color.rs:39-43 (f32::min/max ignore NaN)
+    return c3(fmaxf(fminf(a.r, 1.0f), 0.0f), fmaxf(fminf(a.g, 1.0f), 0.0f), fmaxf(fminf(a.b, 1.0f), 0.0f));
+}
+
+// Rust `f32 as u8` / `f32 as i32`: truncate, saturate, NaN -> 0.
+__device__ __forceinline__ uint32_t f32_to_u8(float v) {
+    if (!(v > 0.0f)) return 0u;
+    if (v >= 255.0f) return 255u;
+    return (uint32_t)v;
+}
+__device__ __forceinline__ int32_t f32_to_i32(float v) {
+    if (v != v) return 0;
+    if (v >= 2147483648.0f) return 2147483647;
+    if (v < -2147483648.0f) return (-2147483647 - 1);
+    return (int32_t)v;
+}
+
+// Region visit counts (diagnostic build -DRG_REGION_STATS; scripts/region_stats.py): every time a
+// wave enters region k, its first active lane adds 1 to counters[RG_REGION_BASE + 2k] and the
+// active lanes to [+ 2k + 1] -- the dynamic weights of the static ISA budget (scripts/isa_budget.py).
+// Words 144.. lie in the lines of tile-queue heads 8-15, unused with RG_NQ = 8.
+#define RG_REGION_BASE 144
+enum : int {
+    RGR_LOOP = 0, RGR_PRIM, RGR_PRIM_SPH_TAIL, RGR_PRIM_PLANE_DIV, RGR_GETCOLOR, RGR_NORMAL_SPHERE,
+    RGR_BATCH, RGR_TEXEL, RGR_UV_SPHERE, RGR_UV_PLANE, RGR_LIGHT_SPH, RGR_REFRACT, RGR_SHADE, RGR_UNWIND,
+    RGR_UNWIND_STEP, RGR_TILE_FETCH, RGR_Q_CLOSEST, RGR_Q_SHADOW, RGR_SH_GROUP, RGR_SH_TAIL, RGR_SH_PLANE,
+    RGR_SH_PLANE_DIV, RGR_QC_GROUP, RGR_QC_TAIL, RGR_QC_PLANE, RGR_PRIM_GROUP, RGR_PRIM_PLANE, RGR_DISK, RGR_BOX,
+    RGR_PUSH_REFL, RGR_PUSH_REFR, RGR_UNWIND_REFRT, RGR_ERROR, RGR_SH_PAIR, RGR_PRIM_PAIR, RGR_QC_PAIR,
+    RGR_WALK, RGR_WALK_LEAF, RGR_LB_SHADOW, RGR_COUNT
+};
+static_assert(RG_REGION_BASE + 2 * RGR_COUNT <= 16 + 16 * 15, "region counters stay below tile-queue head 15");
+#ifdef RG_REGION_STATS
+#define RG_REGION(k)                                                                                  \
+    do {                                                                                              \
+        const unsigned long long m_ = __ballot(1);                                                    \
+        if ((int)(threadIdx.x & 63u) == __builtin_ffsll((long long)m_) - 1) {                         \
+            atomicAdd(&a.counters[RG_REGION_BASE + 2 * (k)], 1ull);                                   \
+            atomicAdd(&a.counters[RG_REGION_BASE + 2 * (k) + 1], (unsigned long long)__builtin_popcountll(m_)); \
+        }                                                                                             \
+    } while (0)
+#else
+#define RG_REGION(k) do { } while (0)
+#endif
+
+__device__ __forceinline__ void raise_error(const RgKernelArgs &a, uint32_t pixel, int status) {
+    RG_REGION(RGR_ERROR);
+    // lowest pixel wins: max of the complemented key; 0 (memset) = no error
+    unsigned long long key = ((unsigned long long)pixel << 8) | (unsigned long long)(-status);
+    atomicMax(&a.counters[3], ~key);
+    if (a.err_sticky) atomicMax(a.err_sticky, ~key);  // survives the next launch's counter reset
+}
+
+}  // namespace rgk

@@ -287,7 +287,7 @@ rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_
     RgKernelArgs a = fill_args(s, d, cx, out_rows);
     const int frames = frames_needed(s->max_depth);
     // host-frame launches of heavy-path scenes run array-frame kernels with the
-    // host-frame features (rg_kernels.hip HF) up to rg_host_array_frames() frames;
+    // host-frame features (rg_render_kernel.h HF) up to rg_host_array_frames() frames;
     // the others the MAXD == 0 kernels, whose frames live in a global buffer
     const bool host_arrays = frames <= rg_host_array_frames() && rg_heavy_path(a);
     const int disp = (d.host_frame && !host_arrays) ? std::max(frames, rg_max_array_frames() + 1) : frames;
@@ -375,7 +375,7 @@ rg_status rg_render_tiles_async(const rg_scene *s, uint32_t width, uint32_t heig
 rg_status rg_render_tiles_pipelined(const rg_scene *s, uint32_t width, uint32_t height, const rg_tiling *tiling,
                                     uint8_t *rgba_dev, float *rgb_dev, void *stream) {
     // one of several frames in flight (rg_frames, bench.py): the heavy path sizes
-    // its grid for throughput (rg_kernels.hip launch_one, RgKernelArgs::pipelined)
+    // its grid for throughput (rg_render_launch.h launch_one, RgKernelArgs::pipelined)
     rg_launch_desc d = device_frame(width, height, tiling, rgba_dev, rgb_dev, static_cast<hipStream_t>(stream));
     d.pipelined = true;
     return rg_launch_tiles(s, d);

@@ -1,6 +1,6 @@
-// rg_launchers.h — the launchers rg_kernels.hip and rg_resolve.hip define for the
-// host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  rg_kernels.hip does not include
-// this header: a change to a launcher's signature there is repeated here.
+// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip and rg_resolve.hip
+// define for the host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  The defining files
+// include this header too, so the compiler checks every signature against it.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -4,7 +4,7 @@
 // point of the cell could hit (cell lookup: rg_lightbuf_ray.h).  The shadow
 // query of the reference (rendering.rs:141-155: trace the ray, in light iff no
 // hit or the closest hit is beyond the light) is an any-hit question on this
-// path (rg_kernels.hip "shadow rays are any-hit"), so a ray that tests its
+// path (rg_k_trace.h "shadow rays are any-hit"), so a ray that tests its
 // cell's spheres -- each with the exact reference test, f32 pre-filter first --
 // gets the answer of the brute-force scan as long as no sphere the exact test
 // could accept is missing from its cell.  The lists are built so it cannot be.

@@ -1,5 +1,5 @@
 // rg_lightbuf_ray.h — the cell lookup of the shadow-ray light buffers, shared by
-// the kernel (rg_kernels.hip) and the CPU check (tests/native/lightbuf_sim.cpp),
+// the kernel (rg_k_bvh.h) and the CPU check (tests/native/lightbuf_sim.cpp),
 // so the host test exercises the very expressions the GPU runs.
 //
 // A light buffer (rg_lightbuf.cpp, built per light at rg_scene_create) lists,

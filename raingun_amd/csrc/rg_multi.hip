@@ -408,7 +408,7 @@ rg_status render_gather(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
 // Direct path into a page-locked caller frame, one launch per device: every
 // device's kernel stores its finished tiles over its OWN PCIe link straight into
 // their image rows (RgKernelArgs::image_rows; the host-frame kernels' LDS tile
-// ring / per-tile stores, rg_kernels.hip), so the copy overlaps the render and
+// ring / per-tile stores, rg_render_kernel.h), so the copy overlaps the render and
 // no band waits for a DMA -- a device's time is its render latency or its rows'
 // PCIe time, whichever is longer.
 rg_status render_direct_one(const rg_scene *s, rg_multi_res *m, uint8_t *dst, rg_stats *stats) {

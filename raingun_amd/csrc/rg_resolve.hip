@@ -35,7 +35,7 @@ struct RgResolveArgs {
     uint32_t vec_out;   // W % 4 == 0 and both outputs 16-B aligned: 16-B stores
 };
 
-// Rust `f32 as u8`: truncate, saturate, NaN -> 0 (rg_kernels.hip f32_to_u8).
+// Rust `f32 as u8`: truncate, saturate, NaN -> 0 (rg_k_math.h f32_to_u8).
 __device__ __forceinline__ uint32_t resolve_u8(float v) {
     if (!(v > 0.0f)) return 0u;
     if (v >= 255.0f) return 255u;

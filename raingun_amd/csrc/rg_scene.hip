@@ -48,7 +48,7 @@ float f32_up(double v) {
     return f;
 }
 
-// f32 pre-filter records of one sphere (bound derivation: rg_kernels.hip, "f32 pre-filter").
+// f32 pre-filter records of one sphere (bound derivation: rg_k_intersect.h, "f32 pre-filter").
 void make_filter_records(const double *p, RgSphF &f, RgSphF2 &f2) {
     const double u = 5.9604644775390625e-08;  // 2^-24
     const double r2 = p[3] * p[3];            // the reference's radius * radius (bodies.rs:97)
@@ -71,7 +71,7 @@ double fov_adjustment(double fov) { return std::tan(fov * (3.1415926535897932384
 int body_params(uint32_t kind) { return kind == RG_BODY_SPHERE ? 4 : kind == RG_BODY_DISK ? 7 : 6; }
 
 // A body or light parameter that is non-finite or >= 1e100 in magnitude: ray
-// arithmetic may then overflow to NaN distances (rg_kernels.hip ray_exotic).
+// arithmetic may then overflow to NaN distances (rg_k_trace.h ray_exotic).
 bool exotic_value(double v) { return !(std::fabs(v) < 1e100); }
 
 void release(rg_scene *s) {
@@ -205,7 +205,7 @@ RgKernelArgs rg_make_args(const rg_scene *s) {
     const bool lane = bvh && rg_heavy_path(a) && s->lane_stack > 0 && s->lane_min_depth < 1 << 20;
     a.lane_stack = lane ? s->lane_stack : 0;
     a.lane_min_depth = lane ? s->lane_min_depth : 1 << 30;
-    // lane_stack entries + one spare slot per lane (rg_kernels.hip bvh_lane, RG_LANE_BRANCHFREE)
+    // lane_stack entries + one spare slot per lane (rg_k_bvh.h bvh_lane, RG_LANE_BRANCHFREE)
     a.lds_lstack_bytes = lane ? ((uint32_t)(a.lane_stack + 1) * 4u) * 256u * RG_HEAVY_WPS : 0u;
     // LDS arena: [lane stacks | sphf | sphf2 | sph | cc (padded to 16 B) | nodes | pln | dsk | box (padded) |
     //             lights | texs (padded) | bodies | mats].  The hot part (staged whenever the sphere

@@ -4,7 +4,7 @@
 // largest area).  This model collapses the SAME binary tree (rg_bvh.cpp's Builder, included below)
 // to W-wide nodes for W = 2, 4, 8, with the product's margin and f32 rounding, and walks it the way
 // the kernel's per-lane walk does (nearest-first, one node per iteration, every child box tested,
-// internal children pushed by entry distance; rg_kernels.hip bvh_lane): per ray kind it counts
+// internal children pushed by entry distance; rg_k_bvh.h bvh_lane): per ray kind it counts
 // walk iterations (node visits: the dependent loads of the walk), child box tests (the f32 VALU of
 // the walk) and exact sphere tests (the f64 VALU), and the worst-case per-lane stack the tree needs
 // (rg_bvh.cpp lane_stack_need).  Every BVH answer is checked against the brute-force scan.

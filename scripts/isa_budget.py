@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """ISA instruction budget of one rg_render_kernel instantiation, by region of the render loop.
 
-Static side: rg_kernels.hip is compiled for gfx950 with line tables, the kernel disassembled, and
+Static side: rg_render_light_d8.hip (--heavy: rg_render_heavy_d8.hip) is compiled for gfx950 with
+line tables, the kernel disassembled, and
 every instruction's full inline chain read back (llvm-symbolizer --inlines), so an instruction of an
 inlined sqrt or dot is attributed to the call site it serves.  Regions are the RG_REGION(k) markers
 of the kernel (-DRG_REGION_STATS counts how often a wave enters each): a marker's static extent is
@@ -35,7 +36,8 @@ import sys
 from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent.parent / "raingun_amd" / "csrc"
-SRC = CSRC / "rg_kernels.hip"
+# the headers that hold the kernel's device code: instructions are attributed by (file, line)
+SRCS = {p.name: p for p in sorted(CSRC.glob("rg_k_*.h")) + [CSRC / "rg_render_kernel.h"]}
 DEFAULT = "_Z16rg_render_kernelILi8ELb1ELb1ELi4ELi3ELb0ELb0ELb0ELi0ELb0EEv12RgKernelArgs"
 LLVM = "/opt/rocm/lib/llvm/bin"
 # callers of sphere_tail -> the pair region its inlined instructions belong to
@@ -46,7 +48,7 @@ VALU = CLASSES[:4]
 
 
 def region_names():
-    txt = SRC.read_text()
+    txt = SRCS["rg_k_math.h"].read_text()
     body = txt[txt.index("RGR_LOOP = 0"):txt.index("RGR_COUNT")]
     return [n.split("=")[0].strip() for n in body.replace("\n", " ").split(",") if n.strip()]
 
@@ -88,27 +90,30 @@ def func_at(lines, li):
 
 
 def regions():
-    """[(region, function name, first line, last line)] -- innermost-first matching by extent size."""
-    lines = SRC.read_text().splitlines()
+    """[(region, function name, file, first line, last line)] -- innermost-first matching by extent size."""
     out = []
-    for i, l in enumerate(lines, 1):
-        for m in re.finditer(r"RG_REGION\((RGR_\w+)\)", l):
-            name = m.group(1)
-            if "#define" in l:
-                continue
-            stripped = l.strip()
-            if stripped.startswith("if (") and not stripped.endswith("{"):
-                continue  # conditional one-line markers: function-level regions below
-            a, b = block_of(lines, i)
-            f = func_at(lines, i)
-            if f in ("rg_render_kernel",) or "rg_render_kernel" in lines[a - 1]:
-                f = "rg_render_kernel"
-            out.append((name, f, a, b))
+    text = {name: p.read_text().splitlines() for name, p in SRCS.items()}
+    for fname, lines in text.items():
+        for i, l in enumerate(lines, 1):
+            for m in re.finditer(r"RG_REGION\((RGR_\w+)\)", l):
+                name = m.group(1)
+                if "#define" in l:
+                    continue
+                stripped = l.strip()
+                if stripped.startswith("if (") and not stripped.endswith("{"):
+                    continue  # conditional one-line markers: function-level regions below
+                a, b = block_of(lines, i)
+                f = func_at(lines, i)
+                if f in ("rg_render_kernel",) or "rg_render_kernel" in lines[a - 1]:
+                    f = "rg_render_kernel"
+                out.append((name, f, fname, a, b))
 
-    def fn_lines(fname, key_start, key_end=None):
+    lines = text["rg_k_shade.h"]
+
+    def fn_lines(func, key_start, key_end=None):
         s = next(i for i, l in enumerate(lines, 1) if key_start in l)
         e = s if key_end is None else next(i for i, l in enumerate(lines[s - 1:], s) if key_end in l)
-        return (fname, s, e)
+        return (func, "rg_k_shade.h", s, e)
     extra = [("RGR_NORMAL_SPHERE",) + fn_lines("surface_normal", "if (b.kind == RG_BODY_SPHERE) { n = normalize"),
              ("RGR_TEXEL",) + fn_lines("texel_fetch", "uint32_t texel_fetch(", "return tg[(size_t)y"),
              ("RGR_UV_SPHERE",) + fn_lines("texture_coords", "const float2 uv = sphere_uv(", "ty = uv.y;"),
@@ -116,7 +121,7 @@ def regions():
              ("RGR_LIGHT_SPH",) + fn_lines("light_dir_dist", "V3 v = sub(v3(l.v[0], l.v[1], l.v[2]), p);", "dist = m;"),
              ("RGR_LIGHT_SPH",) + fn_lines("light_intensity", "V3 d = sub(v3(l.v[0], l.v[1], l.v[2]), p);",
                                            "return l.intensity / (4.0f * PI_F * r2);")]
-    return out + [(r, f, a, b) for r, f, a, b in extra]
+    return out + extra
 
 
 def klass(op: str) -> str:
@@ -180,27 +185,26 @@ def main():
             del args[k:k + 2]
             kernel, out_json, visits_path = ((v, out_json, visits_path) if flag == "--kernel" else
                                              (kernel, v, visits_path) if flag == "--json" else (kernel, out_json, v))
-    dev_only = "-DRG_DEV_LIGHT_ONLY"
+    unit = "rg_render_light_d8"
     if "--heavy" in args:  # the heavy-path instantiations (give their --kernel)
         args.remove("--heavy")
-        dev_only = "-DRG_DEV_HEAVY_ONLY"
+        unit = "rg_render_heavy_d8"
     build = "stats"
     if "--build" in args:
         k = args.index("--build"); build = args[k + 1]; del args[k:k + 2]
     tmp = Path("/tmp/rg_isa_budget")
     tmp.mkdir(exist_ok=True)
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-           "-fPIC", "-gline-tables-only", dev_only, "-DRG_DEV_ONE_DEPTH", "-c", "rg_kernels.hip",
+           "-fPIC", "-gline-tables-only", "-c", unit + ".hip",
            "-o", str(tmp / "k.o"), "--save-temps=obj", *(["-DRG_REGION_STATS"] if build == "stats" else []), *args]
     r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stderr[-3000:])
         sys.exit(1)
-    obj = tmp / "rg_kernels-hip-amdgcn-amd-amdhsa-gfx950.out"
+    obj = tmp / (unit + "-hip-amdgcn-amd-amdhsa-gfx950.out")
     regs = regions()
     names = region_names()
-    src_lines = SRC.read_text().splitlines()
-    marker_line = {i: m.group(1) for i, l in enumerate(src_lines, 1)
+    marker_line = {(fname, i): m.group(1) for fname, p in SRCS.items() for i, l in enumerate(p.read_text().splitlines(), 1)
                    for m in [re.search(r"RG_REGION\((RGR_\w+)\)", l)] if m and "#define" not in l}
     markers = []  # (region, {full names on the chain}) per marker atomic
     per_inst = {}
@@ -210,10 +214,10 @@ def main():
         ch = chains(obj, [a for a, _ in insts])
         for (addr, op), chain in zip(insts, ch):
             reg, inst = tag, sym
-            mk = next(((fname, line) for _, fname, line, _ in chain if fname == "rg_kernels.hip"), None)
-            if build == "stats" and mk and mk[1] in marker_line:
+            mk = next(((fname, line) for _, fname, line, _ in chain if fname in SRCS), None)
+            if build == "stats" and mk in marker_line:
                 if op.startswith("global_atomic_add"):
-                    markers.append((marker_line[mk[1]], {fr[3] for fr in chain}))
+                    markers.append((marker_line[mk], {fr[3] for fr in chain}))
                 continue  # the instrumentation itself
             tail = next((i for i, fr in enumerate(chain) if fr[0] == "sphere_tail"), None)
             if reg is None and tail is not None and tail + 1 < len(chain) and chain[tail + 1][0] in PAIR_OF:
@@ -221,10 +225,10 @@ def main():
             if reg is None:
                 best = None
                 for depth, (f, fname, line, full) in enumerate(chain):  # innermost first
-                    if fname != "rg_kernels.hip":
+                    if fname not in SRCS:
                         continue
-                    for rn, rf, a, b in regs:
-                        if rf == f and a <= line <= b:
+                    for rn, rf, rfile, a, b in regs:
+                        if rf == f and rfile == fname and a <= line <= b:
                             if best is None or (depth, b - a) < best[0]:
                                 best = ((depth, b - a), rn, full)
                     if best is not None:

@@ -3,7 +3,7 @@
 scripts/build_variants.sh region="-DRG_REGION_STATS", run with RAINGUN_HIP_LIB=abvar/region/...).
 
 One whole-frame launch (the headline instantiation: 3840x2160, 16 tiles per wave) per workload;
-prints, per RG_REGION marker (rg_kernels.hip), how many times a wave entered the region and the
+prints, per RG_REGION marker (rg_k_math.h), how many times a wave entered the region and the
 mean active lanes on entry.  scripts/isa_budget.py --visits multiplies these by each region's
 static instructions.
 
@@ -20,7 +20,7 @@ BASE = 144
 
 
 def names():
-    txt = (Path(__file__).resolve().parents[1] / "raingun_amd" / "csrc" / "rg_kernels.hip").read_text()
+    txt = (Path(__file__).resolve().parents[1] / "raingun_amd" / "csrc" / "rg_k_math.h").read_text()
     body = txt[txt.index("RGR_LOOP = 0"):txt.index("RGR_COUNT")]
     return [n.split("=")[0].strip() for n in body.replace("\n", " ").split(",") if n.strip()]
 

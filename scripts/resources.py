@@ -2,8 +2,8 @@
 
     python scripts/resources.py [extra hipcc flags...]
 
-Compiles rg_kernels.hip with the library's flags and -Rpass-analysis=kernel-resource-usage
-and prints VGPRs, spilled VGPRs, scratch bytes per lane, occupancy and static LDS for the
+Compiles the three depth-8 files (rg_render_heavy_d8_host.hip, rg_render_light_d8.hip,
+rg_render_heavy_d8.hip) with the library's flags and -Rpass-analysis=kernel-resource-usage and prints VGPRs, spilled VGPRs, scratch bytes per lane, occupancy and static LDS for the
 MAXD = 8 instantiations (the ones the bench configurations run; "host": the
 host-frame ones, "tpw=-1": the light path's persistent single launches)."""
 import re
@@ -12,15 +12,19 @@ import sys
 from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent.parent / "raingun_amd" / "csrc"
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-       "-fPIC", "-c", "rg_kernels.hip", "-o", "/tmp/rg_kernels_res.o", "-Rpass-analysis=kernel-resource-usage",
-       *sys.argv[1:]]
-out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
-if out.returncode != 0:
-    sys.stderr.write(out.stderr[-4000:])
-    sys.exit(out.returncode)
+UNITS = ["rg_render_heavy_d8_host", "rg_render_light_d8", "rg_render_heavy_d8"]
+procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
+                           "-fno-fast-math", "-fPIC", "-c", u + ".hip", "-o", f"/tmp/{u}_res.o",
+                           "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:]],
+                          cwd=CSRC, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True) for u in UNITS]
+remarks = []
+for p, err in [(p, p.communicate()[1]) for p in procs]:
+    if p.returncode != 0:
+        sys.stderr.write(err[-4000:])
+        sys.exit(p.returncode)
+    remarks += err.splitlines()
 rows, cur = [], None
-for line in out.stderr.splitlines():
+for line in remarks:
     m = re.search(r"Function Name: (\S+)", line)
     if m:
         cur = {"name": m.group(1)}

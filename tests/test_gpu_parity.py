@@ -94,6 +94,7 @@ def test_config3_test3_4k(oracle_lib, example_scenes):
     (200, 2, 0, 160, 90),
     (200, 2, 1, 160, 90),
     (200, 2, 2, 160, 90),
+    (40, 4, 12, 160, 90),  # 9-16 frames: the MAXD = 16 kernels (rg_render_light_d16.hip, rg_render_heavy_d16.hip)
     (40, 4, 20, 160, 90),
 ])
 @pytest.mark.parametrize("path,bvh,lane", PATH_BVH)
@@ -105,7 +106,7 @@ def test_synthetic(oracle_lib, n, planes, depth, w, h, path, bvh, lane):
 @pytest.mark.parametrize("path", PATHS)
 def test_light_counts(oracle_lib, example_scenes, keep, path):
     """test1 with 1, 2 or 3 of its lights: the light path runs a 2-light shadow batch for scenes
-    with at most RG_LB_SMALL (2) lights and the 3-light one otherwise (rg_kernels.hip launch_depth)."""
+    with at most RG_LB_SMALL (2) lights and the 3-light one otherwise (rg_render_launch.h launch_light)."""
     scene = copy.deepcopy(example_scenes["test1"])
     scene.lights = [scene.lights[i] for i in keep]
     _compare(oracle_lib, scene, 320, 240, path=path)

@@ -107,7 +107,7 @@ def test_depth_zero_still_shades_primary(oracle_lib, example_scenes):
 
 def test_u8_div255_residual_form_is_exact(tmp_path):
     """The kernel converts texel bytes with q0 = b * (1/255); q = fma(fma(-q0, 255, b), 1/255, q0)
-    (rg_kernels.hip u8_div255) instead of the IEEE division the reference does (b as f32 / 255.0).
+    (rg_k_shade.h u8_div255) instead of the IEEE division the reference does (b as f32 / 255.0).
     Check, for all 256 byte values, that both give the same f32 (C fmaf, no contraction)."""
     import shutil
     import subprocess
