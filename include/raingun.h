@@ -218,6 +218,43 @@ rg_status rg_render_aa_async(const rg_scene *scene, uint32_t width, uint32_t hei
 rg_status rg_resolve_box(int32_t device, const float *rgb_in, uint32_t width, uint32_t height,
                          uint32_t samples, uint8_t *rgba_out, float *rgb_out);
 
+/* Adaptive anti-aliasing: rg_render_image_aa that traces the samples x samples rays only of
+ * pixels on edges of the 1-sample frame.  With `base` the frame of rg_render_image:
+ *   contrast  m(p) = max |base[p][c] - base[q][c]| as integers, over c in {R, G, B} and the up
+ *             to eight neighbours q of p inside the frame (0 without neighbours; alpha ignored)
+ *   mask      flag(p) = m(p) >= threshold (0..256: 0 flags every pixel, 256 none)
+ *   pixel     flagged: the box resolve of its samples x samples samples, exactly as
+ *             rg_render_image_aa; unflagged: the base pixel's bytes, and for `rgb_out` its f32
+ *             RGB clamped as a sample (the samples = 1 resolve)
+ * `mask_out` (nullable, host, width*height bytes) receives the mask, 1 = supersampled.  Rays
+ * (`stats`): for threshold >= 1 and samples >= 2 those of the base frame plus those of exactly
+ * the samples*samples samples of every flagged pixel (primary == width*height +
+ * samples*samples*flagged); threshold 0 is rg_render_image_aa (no base pass), samples 1 is
+ * rg_render_image (the mask is still produced).  On a device error the frame is still
+ * delivered and stats->error_pixel is the lower of the base pass's failing pixel and the output
+ * pixel that contains the lowest-index failing traced sample, the status that pixel's (a tie:
+ * the base pass's).  Arguments as rg_render_image_aa, and RG_ERR_INVALID_ARGUMENT for
+ * threshold > 256.  raingun_amd/aa.py restates the result in numpy (resolve_adaptive). */
+rg_status rg_render_image_aa_adaptive(const rg_scene *scene, uint32_t width, uint32_t height,
+                                      uint32_t samples, uint32_t threshold, uint8_t *rgba_out,
+                                      float *rgb_out, uint8_t *mask_out, rg_stats *stats);
+
+/* Device-resident rg_render_image_aa_adaptive: `rgba_dev`, `rgb_dev` (nullable) and `mask_dev`
+ * (nullable) are device pointers on the scene's device.  The work is ordered after everything
+ * enqueued on `stream` so far and later work on `stream` after it.  BLOCKING: the host reads
+ * the per-band tile counts between the 1-sample pass and the sample launches, and the call
+ * returns with `stream` idle.  `stats` nullable. */
+rg_status rg_render_aa_adaptive(const rg_scene *scene, uint32_t width, uint32_t height,
+                                uint32_t samples, uint32_t threshold, uint8_t *rgba_dev,
+                                float *rgb_dev, uint8_t *mask_dev, void *stream, rg_stats *stats);
+
+/* The edge detector of rg_render_image_aa_adaptive alone, on `device`, host buffers, blocking
+ * (as rg_resolve_box): `rgba_in` width*height packed RGBA8 pixels (any shape: portrait too),
+ * `mask_out` width*height bytes, *flagged (nullable) the number of ones.
+ * RG_ERR_INVALID_ARGUMENT for null buffers, zero sizes, threshold > 256 or 2^32 pixels or more. */
+rg_status rg_edge_mask(int32_t device, const uint8_t *rgba_in, uint32_t width, uint32_t height,
+                       uint32_t threshold, uint8_t *mask_out, uint32_t *flagged);
+
 /* Page-lock a caller buffer (hipHostRegister) so rg_render_image / rg_render_tiles
  * / rg_render_multi DMA straight into it; unregister before freeing it.  Optional:
  * pageable buffers work too (staged).  A Rust caller registers its

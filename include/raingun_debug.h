@@ -101,6 +101,18 @@ rg_status rg_debug_set_host_tile_shape(rg_scene *scene, int32_t tile_wlog);
  * small bands so that small frames span several.  Results are identical for every value. */
 rg_status rg_debug_set_aa_band_rows(rg_scene *scene, int32_t rows);
 
+/* Adaptive anti-aliasing (rg_render_image_aa_adaptive / rg_render_aa_adaptive), a probe for
+ * scripts/aa_adaptive_bench.py.  rg_debug_set_aa_adaptive_timing(enable != 0): the following
+ * calls record HIP events around their passes.  rg_debug_aa_adaptive_info, of the scene's
+ * latest call that ran the passes (threshold >= 1): ms[0] the 1-sample frame, ms[1] the mask
+ * kernel, ms[2] the tile-list kernel, ms[3] the sparse renders and ms[4] the adaptive resolves,
+ * each summed over the bands (bands on the two render streams overlap, so the sums may exceed
+ * the call's span; all zero without timing); *flagged the flagged pixels, *listed_tiles the
+ * sample tiles launched, *bands_launched the bands that had any.  Every pointer nullable. */
+rg_status rg_debug_set_aa_adaptive_timing(rg_scene *scene, int32_t enable);
+rg_status rg_debug_aa_adaptive_info(const rg_scene *scene, float ms[5], uint32_t *flagged, uint32_t *listed_tiles,
+                                    uint32_t *bands_launched);
+
 /* rg_render_multi: mode 0 (default) = every device delivers its rows of the
  * frame to the host buffer itself, over its own PCIe link: `bands` = -1 one
  * launch per device whose kernel stores its rows straight into a page-locked

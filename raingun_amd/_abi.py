@@ -140,13 +140,17 @@ EXPORTED_SYMBOLS = (
     "rg_render_image_aa",
     "rg_render_aa_async",
     "rg_resolve_box",
+    "rg_render_image_aa_adaptive",
+    "rg_render_aa_adaptive",
+    "rg_edge_mask",
 )
 # include/raingun_debug.h
 DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "rg_debug_counters",
                  "rg_debug_set_lightbuf", "rg_debug_lightbuf_count",
                  "rg_debug_set_tile_order", "rg_debug_set_lane_depth", "rg_debug_set_image_bands", "rg_debug_set_host_split",
                  "rg_debug_fail_split_a", "rg_debug_set_host_ring", "rg_debug_set_host_tile_shape", "rg_debug_set_multi", "rg_debug_gather_noop",
-                 "rg_debug_counter_words", "rg_debug_set_aa_band_rows")
+                 "rg_debug_counter_words", "rg_debug_set_aa_band_rows",
+                 "rg_debug_set_aa_adaptive_timing", "rg_debug_aa_adaptive_info")
 # include/raingun_frames.h
 FRAMES_SYMBOLS = ("rg_frames_create", "rg_frames_destroy", "rg_frames_step", "rg_frames_flush", "rg_frames_image",
                   "rg_frames_read_image", "rg_frames_status", "rg_frames_set_batch", "rg_frames_set_root_tiles", "rg_comm_id_bytes",
@@ -270,6 +274,20 @@ def _declare(lib: C.CDLL) -> None:
                                        C.c_void_p]
         lib.rg_debug_set_aa_band_rows.restype = C.c_int32
         lib.rg_debug_set_aa_band_rows.argtypes = [C.c_void_p, C.c_int32]
+    if hasattr(lib, "rg_render_image_aa_adaptive"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
+        lib.rg_render_image_aa_adaptive.restype = C.c_int32
+        lib.rg_render_image_aa_adaptive.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, P(rg_stats)]
+        lib.rg_render_aa_adaptive.restype = C.c_int32
+        lib.rg_render_aa_adaptive.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, P(rg_stats)]
+        lib.rg_debug_set_aa_adaptive_timing.restype = C.c_int32
+        lib.rg_debug_set_aa_adaptive_timing.argtypes = [C.c_void_p, C.c_int32]
+        lib.rg_debug_aa_adaptive_info.restype = C.c_int32
+        lib.rg_debug_aa_adaptive_info.argtypes = [C.c_void_p, P(C.c_float), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
+        lib.rg_edge_mask.restype = C.c_int32
+        lib.rg_edge_mask.argtypes = [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                     P(C.c_uint32)]
     lib.rg_frames_status.restype = C.c_int32
     lib.rg_frames_status.argtypes = [C.c_void_p, P(C.c_int32)]
     if hasattr(lib, "rg_frames_set_batch"):  # absent from pre-round-3 builds

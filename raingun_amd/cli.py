@@ -1,6 +1,6 @@
 """`raingun` command line, mirroring the reference's src/main.rs + src/render.rs.
 
-    python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [-o FILE] FILE
+    python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
@@ -9,7 +9,10 @@ each other (the last one wins); explicit --width/--height override presets
 (but not --draft, which clap treats as overriding them, main.rs:47-54).
 `--samples N` (1..8, default 1; not in the reference) renders N x N rays per
 pixel on the regular sub-pixel grid and box-filters them (rg_render_image_aa);
---draft leaves it alone.  The
+--draft leaves it alone.  `--adaptive T` (0..256; not in the reference) spends
+the N x N rays only on pixels whose 8-neighbourhood contrast in the 1-sample
+frame is at least T (rg_render_image_aa_adaptive); with --samples 1 it is
+accepted and has no effect.  The
 render itself runs on the GPU (rg_render_image); the scene is loaded and the
 PNG written by the native host layer (libraingun_host.so), and the timing line matches
 print_render_message (render.rs:218-244).  `--preview` (piston window) is not
@@ -33,6 +36,7 @@ class RenderOptions:          # render.rs:32-46
     height: int = 600
     max_recursion_depth: Optional[int] = None
     samples: int = 1          # N x N rays per pixel (--samples; not in the reference)
+    adaptive: Optional[int] = None  # contrast threshold of adaptive anti-aliasing (--adaptive)
 
 
 class _LastWins(argparse.Action):
@@ -61,6 +65,9 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("--gpu", type=int, default=0, help="HIP device to render on.")
     p.add_argument("--samples", metavar="N",
                    help="Anti-aliasing: N x N rays per pixel on a regular grid, box-filtered (1..8, default 1).")
+    p.add_argument("--adaptive", metavar="T",
+                   help="Adaptive anti-aliasing: the N x N rays only where the 8-neighbourhood contrast of the "
+                        "1-sample frame is at least T (0..256).")
     p.add_argument("input", metavar="FILE", help="The scene definition file, in YAML format.")
     return p
 
@@ -71,6 +78,10 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
         o.samples = _parse_u32(ns.samples, "Could not parse samples")
         if not 1 <= o.samples <= 8:
             raise SystemExit("samples must be between 1 and 8")
+    if ns.adaptive is not None:
+        o.adaptive = _parse_u32(ns.adaptive, "Could not parse adaptive")
+        if not 0 <= o.adaptive <= 256:
+            raise SystemExit("adaptive must be between 0 and 256")
     if ns.draft:
         o.max_recursion_depth = 4
     elif ns.hd:
@@ -145,7 +156,9 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
 
     ds = DeviceScene(scene, device=ns.gpu)
     t0 = time.perf_counter()                     # render.rs:54-56
-    if opts.samples > 1:
+    if opts.samples > 1 and opts.adaptive is not None:
+        img = ds.render_image_aa_adaptive(opts.width, opts.height, opts.samples, opts.adaptive)
+    elif opts.samples > 1:
         img = ds.render_image_aa(opts.width, opts.height, opts.samples)
     else:
         img = ds.render_image(opts.width, opts.height)

@@ -13,6 +13,13 @@
 // 16 B per sample) stays within this; two such slots, one per render stream
 #define RG_AA_SLOT_BYTES ((size_t)64 << 20)
 #endif
+#ifndef RG_AA_ADAPTIVE_SLOT_BYTES
+// adaptive anti-aliasing (rg_aa.hip "adaptive"): its bands' sparse launches hold a fraction of a
+// band's tiles, so they want larger bands: 4K, k = 4, T = 32 at 64 / 136 / 272 / 544 output rows
+// per band: test1 4.26 / 3.29 / 2.88 / 2.64 ms, north star 16.7 / 12.6 / 10.7 / 10.0 ms
+// (DESIGN.md 4p); 256 MiB is 272 rows there
+#define RG_AA_ADAPTIVE_SLOT_BYTES ((size_t)256 << 20)
+#endif
 #define RG_AA_MIN_BAND_ROWS 8  // output rows per band at least (automatic choice)
 
 // `bands` bands of `band_rows` rows of `width` pixels cover host rows [0, host_rows): band b

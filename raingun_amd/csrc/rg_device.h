@@ -207,6 +207,14 @@ struct RgKernelArgs {
     // 0 = RG_HOST_RING for both.  Small launches (rg_render_multi's shares) want small groups (balance),
     // whole frames long runs of host memory per flush (rg_capi.hip host_ring_for)
     uint32_t ring_flush, ring_group;
+    // Sparse launches (the SPARSE instantiations of rg_render_kernel only; adaptive anti-aliasing,
+    // rg_aa.hip): px_mask non-null selects them.  The queue hands out tile_perm[0 .. tile_limit),
+    // a LIST of the launch's 8x8 tiles, and a lane renders its pixel (x, y) only if
+    // px_mask[(y / px_k) * px_w + x / px_k] is non-zero (one byte per px_k x px_k block of the
+    // frame, px_w blocks per row); the other lanes store nothing and count no ray.  At the end of
+    // the struct: the other instantiations keep their argument offsets.
+    const uint8_t *px_mask;
+    uint32_t tile_limit, px_k, px_w;
 };
 
 __host__ __device__ inline uint32_t rg_tile_w(const RgKernelArgs &a) { return 1u << a.tile_wlog; }

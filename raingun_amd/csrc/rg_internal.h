@@ -1,7 +1,7 @@
 // rg_internal.h — host-side state behind the opaque rg_scene handle, shared
 // by rg_scene.hip (scene upload, kernel arguments), rg_launch.hip (per-stream
 // launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
-// streaming, debug setters), rg_aa.hip (supersampled frames), rg_frames.hip
+// streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_frames.hip
 // (frames in flight over N processes) and rg_multi.hip (one process driving N
 // devices).  The band resource set the two kinds of host frames are built on is
 // in rg_bands.h, the band arithmetic in rg_band_plan.h.  Not part of the ABI.
@@ -102,6 +102,25 @@ struct rg_aa_res : rg_band_res {
     void *slot_rgba[2] = {nullptr, nullptr};
     void *slot_rgb[2] = {nullptr, nullptr};
     size_t slot_cap[2] = {0, 0};  // samples
+    // adaptive anti-aliasing (rg_render_image_aa_adaptive / rg_render_aa_adaptive): the 1-sample
+    // pass, the mask and the tile lists run on a stream of their own (a launch context, so a
+    // primary-ray table and a tile order, of the W x H frame beside the bands' of the sample frame)
+    hipStream_t base_stream = nullptr;
+    hipEvent_t ev_list = nullptr;  // the base frame, the mask and the lists are made
+    uint8_t *d_mask = nullptr;     // W x H bytes (when the caller gives no mask buffer)
+    size_t d_mask_cap = 0;
+    uint32_t *d_list = nullptr;    // per band, the listed sample tiles (bands x tiles of a full band)
+    size_t d_list_cap = 0;         // bytes
+    uint32_t *d_counts = nullptr;  // per band its listed tiles, then the mask kernel's sharded flagged counters
+    size_t d_counts_cap = 0;       // bytes
+    uint32_t *h_counts = nullptr;  // pinned: the same, read between the passes
+    size_t h_counts_cap = 0;       // bytes
+    // the probe of include/raingun_debug.h (rg_debug_set_aa_adaptive_timing / rg_debug_aa_adaptive_info)
+    bool timing = false;
+    std::vector<hipEvent_t> ev_mark;  // timing events, in the order the passes record them
+    size_t n_marks = 0;
+    float pass_ms[5] = {0, 0, 0, 0, 0};
+    uint32_t flagged = 0, listed_tiles = 0, bands_launched = 0;
 };
 
 // Everything rg_scene_create uploads, as host tables (kept for replicas on
@@ -228,6 +247,13 @@ struct rg_launch_desc {
     // rgba / rgb pointing at tile_first's first row
     uint32_t tile_first = 0, tile_count = 0xFFFFFFFFu;
     uint32_t tile_group = 1;  // groups of tile_group consecutive image tiles per stride (RgKernelArgs::tile_group)
+    // a sparse launch (px_mask non-null; device-resident 8x8 tiles only): of the launch's tiles only
+    // tile_list[0 .. tile_limit) (device memory) are rendered, and of their pixels (x, y) only those with
+    // px_mask[(y / px_k) * px_w + x / px_k] != 0 (RgKernelArgs::px_mask); the tiles are not reordered
+    const uint32_t *tile_list = nullptr;
+    uint32_t tile_limit = 0;
+    const uint8_t *px_mask = nullptr;
+    uint32_t px_k = 1, px_w = 0;
 };
 
 // Enqueue one tiled render on d.stream (the body of rg_render_tiles_async).

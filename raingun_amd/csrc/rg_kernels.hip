@@ -99,8 +99,7 @@ static bool host_frame_launch(const RgKernelArgs *a) {
 // Does this launch keep its frames in the launch context's global buffer (the
 // host sizes it with rg_render_grid_threads)?  Depths above the arrays.
 extern "C" int rg_launch_global_frames(const RgKernelArgs *a, int maxd) {
-    (void)a;
-    return maxd > rg_max_array_frames();
+    return a->px_mask != nullptr || maxd > rg_max_array_frames();
 }
 
 template <int MAXD, bool HF = false>
@@ -113,6 +112,8 @@ static hipError_t launch_depth(const RgKernelArgs *a, hipStream_t stream, size_t
 }
 
 static hipError_t dispatch_depth(const RgKernelArgs *a, int maxd, hipStream_t stream, size_t *gt) {
+    if (a->px_mask)  // a sparse launch (rg_render_*_sparse.hip): a tile list and a pixel mask, frames in the global buffer
+        return rg_heavy_path(*a) ? launch_heavy<0, false, true>(a, stream, gt) : launch_light<0, true>(a, stream, gt);
     if (host_frame_launch(a)) {
         if (RG_HOST_ARRAY_FRAMES > 0 && maxd <= RG_HOST_ARRAY_FRAMES && rg_heavy_path(*a))
             return launch_depth<8, true>(a, stream, gt);

@@ -40,6 +40,9 @@ rg_status decode_error(unsigned long long word, int32_t *pixel) {
 rg_status validate(const rg_scene *s, const rg_launch_desc &d, uint32_t *out_rows) {
     if (d.tile_wlog < 3 || d.tile_wlog > 6) return RG_ERR_INVALID_ARGUMENT;
     if (d.image_rows && (!d.host_frame || d.rgb)) return RG_ERR_INVALID_ARGUMENT;
+    if (d.px_mask && (!d.tile_list || d.tile_limit == 0 || d.px_k == 0 || d.host_frame || d.tile_wlog != 3 ||
+                      d.tile_flags || d.cancel))
+        return RG_ERR_INVALID_ARGUMENT;
     if (!s || !d.rgba || d.width == 0 || d.height == 0 || !rg_tiling_valid(&d.tiling)) return RG_ERR_INVALID_ARGUMENT;
     if (d.tile_group < 1 ||
         d.tiling.tile_offset + d.tile_group > d.tiling.tile_stride + (d.tile_group == 1 ? 1u : 0u))
@@ -81,6 +84,13 @@ RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, const rg_laun
     a.defer_px = d.host_frame ? 1u : 0u;
     a.image_rows = d.image_rows ? 1u : 0u;
     a.pipelined = d.pipelined ? 1u : 0u;
+    if (d.px_mask) {  // a sparse launch: the list is the queue
+        a.px_mask = d.px_mask;
+        a.px_k = d.px_k;
+        a.px_w = d.px_w;
+        a.tile_perm = d.tile_list;
+        a.tile_limit = d.tile_limit;
+    }
     if (d.host_frame) {  // the light path's LDS tile ring (rg_device.h RG_RING_*)
         const bool big = rg_tile_count(a) >= RG_RING_BIG_TILES;
         a.ring_flush = (uint32_t)std::max(0, big ? s->ring_flush_big : s->ring_flush_small);
@@ -290,12 +300,14 @@ rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_
     // host-frame features (rg_render_kernel.h HF) up to rg_host_array_frames() frames;
     // the others the MAXD == 0 kernels, whose frames live in a global buffer
     const bool host_arrays = frames <= rg_host_array_frames() && rg_heavy_path(a);
-    const int disp = (d.host_frame && !host_arrays) ? std::max(frames, rg_max_array_frames() + 1) : frames;
+    // (so do sparse launches: the SPARSE instantiations exist for MAXD == 0 only)
+    const int disp = ((d.host_frame && !host_arrays) || d.px_mask) ? std::max(frames, rg_max_array_frames() + 1) : frames;
     if ((st = size_deep_frames(cx, a, frames, disp)) != RG_OK) return st;
     if ((st = refresh_prim_table(cx, a, d.stream)) != RG_OK) return st;
     if (!rg_heavy_path(a)) a.lds_blob = rg_lds_blob_for(s, a);  // light path: one staging loop per block
     if (d.timed && !ok(hipEventRecord(cx->ev0, d.stream))) return RG_ERR_DEVICE;  // kernel_ms includes the tile probe
-    if ((st = order_tiles(s, d, cx, a)) != RG_OK) return st;
+    // a sparse launch's list only schedules: no probe, and the cached order and its key stay as they are
+    if (!d.px_mask && (st = order_tiles(s, d, cx, a)) != RG_OK) return st;
     return launch_and_snapshot(d, cx, a, disp);
 }
 

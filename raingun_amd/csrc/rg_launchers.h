@@ -1,4 +1,4 @@
-// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip and rg_resolve.hip
+// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip, rg_resolve.hip and rg_edge.hip
 // define for the host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  The defining files
 // include this header too, so the compiler checks every signature against it.
 #pragma once
@@ -19,3 +19,22 @@ extern "C" hipError_t rg_launch_resolve(const float *in, uint32_t width, uint32_
                                         float *rgb, hipStream_t stream);
 extern "C" hipError_t rg_launch_trace(const RgKernelArgs *a, const double *rays, uint32_t n, double *dist,
                                       int32_t *body, hipStream_t stream);
+// rg_resolve.hip: the resolve of adaptive anti-aliasing over rows x width output pixels: pixels
+// whose mask byte is non-zero become the box resolve of their k x k samples of `in` (nullable:
+// none), the others keep rgba and get their rgb (nullable) clamped in place.
+extern "C" hipError_t rg_launch_resolve_adaptive(const float *in, const uint8_t *mask, uint32_t width, uint32_t rows,
+                                                 uint32_t k, uint8_t *rgba, float *rgb, hipStream_t stream);
+// rg_edge.hip: mask[p] = 1 where the 8-neighbourhood contrast of packed RGBA8 pixel p is >= threshold,
+// else 0.  The number of ones is added to `flagged` (device, zeroed by the caller): RG_EDGE_SHARDS
+// counters, RG_EDGE_SHARD_WORDS words (one 128-B line) apart, whose sum it is -- a 4K frame is 32,400
+// waves, and that many atomics on one address alone take ~0.2 ms (measured: DESIGN.md 4p).
+#define RG_EDGE_SHARDS 64
+#define RG_EDGE_SHARD_WORDS 32
+extern "C" hipError_t rg_launch_edge_mask(const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t threshold,
+                                          uint8_t *mask, uint32_t *flagged, hipStream_t stream);
+// rg_edge.hip: for each of `bands` bands of band_rows output rows (the last partial), the 8x8 sample
+// tiles of the band's k-fold launch that overlap a flagged pixel (rg_sample_tiles.h), appended to
+// list[b * stride ..] with counts[b] (device, zeroed by the caller) += their number.
+extern "C" hipError_t rg_launch_tile_list(const uint8_t *mask, uint32_t width, uint32_t height, uint32_t k,
+                                          uint32_t band_rows, uint32_t bands, uint32_t *list, uint32_t stride,
+                                          uint32_t *counts, hipStream_t stream);

@@ -123,7 +123,9 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
 // tile from an atomic queue (counters[16..], sharded) and runs the per-lane
 // state machine until its 64 lanes have written their pixels.
 template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
-          bool HF = false>
+          bool HF = false, bool SPARSE = false>
+// SPARSE (MAXD == 0 only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
+// renders its pixel only where a.px_mask says so (adaptive anti-aliasing, rg_aa.hip; RgKernelArgs::px_mask).
 // LBT: lights per shadow batch on the light path (2, 3; -1: one light), 1: the heavy path.
 // HF: the host-frame features (HOSTF below) with MAXD array frames.  TPW: light path, tiles per wave (0: RG_LIGHT_TILES_PER_WAVE; < 0: persistent waves that take tiles
 // until the queue is empty -- single launches, whose makespan is their slowest wave's tile sum).  Light path (LBT != 1): blocks of RG_LIGHT_BLOCK_WAVES waves, at least WPS waves
@@ -139,6 +141,7 @@ void rg_render_kernel(RgKernelArgs a) {
     uint32_t wt_tiles = 0;
 #endif
     constexpr bool GFRAMES = MAXD == 0;
+    static_assert(!SPARSE || (MAXD == 0 && !HF), "sparse launches run the MAXD == 0 kernels");
     // the launch context's other counter set (the previous launch's, read back
     // already: same stream) starts the next launch at zero -- no memset per frame
     if (blockIdx.x == 0 && a.counters_next)
@@ -748,7 +751,7 @@ void rg_render_kernel(RgKernelArgs a) {
             }
             // ring mode: the queue hands out groups of RING consecutive tiles (one contiguous
             // run of host memory per ring flush: 4 KB with 64x1 tiles)
-            const uint32_t qlimit = (RING > 0 && use_ring) ? (ntiles + ring_g - 1) / ring_g : ntiles;
+            const uint32_t qlimit = SPARSE ? a.tile_limit : (RING > 0 && use_ring) ? (ntiles + ring_g - 1) / ring_g : ntiles;
             // Tile-slot prefetch (light path, device-resident launches): the slot claimed at the
             // previous tile's start, so the atomic's round trip overlaps that tile (round 4, same
             // box, interleaved: test1 0.2972 -> 0.2939 ms over 200 frames, test3 0.2656 -> 0.2631:
@@ -809,7 +812,8 @@ void rg_render_kernel(RgKernelArgs a) {
                         pf_valid = true;
                     }
                 }
-                if (a.tile_perm) tile = a.tile_perm[tile];  // scheduling order only; every tile is rendered once
+                if constexpr (SPARSE) tile = a.tile_perm[tile];  // the list entry
+                else if (a.tile_perm) tile = a.tile_perm[tile];  // scheduling order only; every tile is rendered once
 #ifdef RG_WAVE_TIMES
                 ++wt_tiles;
 #endif
@@ -835,6 +839,9 @@ void rg_render_kernel(RgKernelArgs a) {
                     if (a.rgb) { a.rgb[3 * oidx] = 0.0f; a.rgb[3 * oidx + 1] = 0.0f; a.rgb[3 * oidx + 2] = 0.0f; }
 #endif
                     alive = false;
+                }
+                if constexpr (SPARSE) {  // once per tile: only the samples of flagged pixels are traced
+                    if (alive) alive = a.px_mask[(size_t)(y / a.px_k) * a.px_w + x / a.px_k] != 0;
                 }
                 pixel = y * a.width + x;
                 if (alive) {

@@ -1,6 +1,6 @@
 // rg_render_launch.h — launch policy of rg_render_kernel: which instantiation a launch runs and
-// with what grid.  launch_light<MAXD> / launch_heavy<MAXD, HF> are instantiated explicitly, one
-// per rg_render_*.hip, so every rg_render_kernel instantiation is emitted by exactly one
+// with what grid.  launch_light<MAXD, SPARSE> / launch_heavy<MAXD, HF, SPARSE> are instantiated explicitly, one
+// per rg_render_*.hip (SPARSE: the launches of a tile list under a pixel mask, MAXD == 0 only), so every rg_render_kernel instantiation is emitted by exactly one
 // translation unit (the occupancy cache and the HIP runtime identify a kernel by its host
 // address); the dispatcher (rg_kernels.hip dispatch_depth) sees only the declarations below.
 #pragma once
@@ -32,7 +32,8 @@ __attribute__((visibility("hidden"))) hipError_t occupancy(const void *kern, int
 
 // Launch (or, with grid_threads != nullptr, only size: the threads of the
 // grid, which a MAXD == 0 launch needs for its frame buffer) one instantiation.
-template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LB, bool F32F, bool BVH, bool TASKS, int TPW = 0, bool HF = false>
+template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LB, bool F32F, bool BVH, bool TASKS, int TPW = 0, bool HF = false,
+          bool SPARSE = false>
 static hipError_t launch_one(const RgKernelArgs *a, size_t lds, hipStream_t stream, size_t *grid_threads) {
     // Block size.  The heavy path shares one LDS copy of the scene (and the
     // BVH stacks / task pool) among the CU's 4*WPS waves: one block per CU.
@@ -42,7 +43,7 @@ static hipError_t launch_one(const RgKernelArgs *a, size_t lds, hipStream_t stre
     // waves that finished (a 4*WPS-wave block would keep the CU until its
     // slowest wave -- one refractive tile -- is done).
     constexpr int threads = LB != 1 ? 64 * RG_LIGHT_BLOCK_WAVES : 256 * WPS;  // LB != 1: the light path
-    auto kern = rg_render_kernel<MAXD, LSPH, LCOLD, WPS, LB, F32F, BVH, TASKS, TPW, HF>;
+    auto kern = rg_render_kernel<MAXD, LSPH, LCOLD, WPS, LB, F32F, BVH, TASKS, TPW, HF, SPARSE>;
     int cus = 0, per_cu = 0;
     const hipError_t oe = occupancy(reinterpret_cast<const void *>(kern), threads, lds, cus, per_cu);
     if (oe != hipSuccess) return oe;
@@ -51,7 +52,8 @@ static hipError_t launch_one(const RgKernelArgs *a, size_t lds, hipStream_t stre
     // blocks per CU (2 per SIMD), never more than the occupancy query admits (a scene whose LDS
     // copy allows fewer would otherwise start the extra blocks only after the queue drained)
     if (MAXD != 0 && LB != 1 && TPW < 0) per_cu = std::min(per_cu, RG_LIGHT_PERSIST_BLOCKS_PER_CU);
-    const unsigned long long tiles = rg_tile_count(*a);
+    // sparse launches: the grid is sized from the tile list, not from the frame
+    const unsigned long long tiles = SPARSE ? a->tile_limit : rg_tile_count(*a);
     const unsigned long long waves = (unsigned long long)threads / 64u;
     unsigned long long blocks = (unsigned long long)cus * per_cu;
     const unsigned long long need = (tiles + waves - 1) / waves;
@@ -91,22 +93,22 @@ static hipError_t launch_one(const RgKernelArgs *a, size_t lds, hipStream_t stre
 #endif
 // RG_HEAVY_SCENE_BODIES and the path decision (rg_heavy_path) live in rg_device.h
 
-template <int MAXD, int WPS, int LB, bool F32F, bool BVH, bool TASKS, int TPW = 0, bool HF = false>
+template <int MAXD, int WPS, int LB, bool F32F, bool BVH, bool TASKS, int TPW = 0, bool HF = false, bool SPARSE = false>
 static hipError_t launch_waves(const RgKernelArgs *a, hipStream_t stream, size_t *gt) {
     // the BVH kernels also hold the static per-wave traversal stacks
     constexpr uint32_t budget = RG_LDS_BUDGET - (BVH ? (uint32_t)sizeof(rg_bvh_stack) : 0u) -
                                 (uint32_t)(MAXD != 0 && !HF ? 0 : (LB != 1 ? RG_LIGHT_BLOCK_WAVES : 4 * WPS) * 64 * 4) -  // tile_px
                                 (TASKS ? (uint32_t)sizeof(TaskPool) : 0u);
     if (a->lds_total_bytes <= budget)  // whole scene (empty sphere part if n_sph == 0)
-        return launch_one<MAXD, true, true, WPS, LB, F32F, BVH, TASKS, TPW, HF>(a, a->lds_total_bytes, stream, gt);
+        return launch_one<MAXD, true, true, WPS, LB, F32F, BVH, TASKS, TPW, HF, SPARSE>(a, a->lds_total_bytes, stream, gt);
     if (a->n_sph > 0 && a->lds_hot_bytes <= budget)
-        return launch_one<MAXD, true, false, WPS, LB, F32F, BVH, TASKS, TPW, HF>(a, a->lds_hot_bytes, stream, gt);
+        return launch_one<MAXD, true, false, WPS, LB, F32F, BVH, TASKS, TPW, HF, SPARSE>(a, a->lds_hot_bytes, stream, gt);
     if constexpr (BVH) {  // the sphere tables do not fit: the BVH nodes alone, after the per-lane walk stacks
         const uint32_t nodes_lds = a->lds_lstack_bytes + (uint32_t)a->n_nodes * (uint32_t)sizeof(RgBvhNode);
         if (a->n_nodes > 0 && nodes_lds <= budget)
-            return launch_one<MAXD, false, true, WPS, LB, F32F, BVH, TASKS, TPW, HF>(a, nodes_lds, stream, gt);
+            return launch_one<MAXD, false, true, WPS, LB, F32F, BVH, TASKS, TPW, HF, SPARSE>(a, nodes_lds, stream, gt);
     }
-    return launch_one<MAXD, false, false, WPS, LB, F32F, BVH, TASKS, TPW, HF>(a, a->lds_lstack_bytes, stream, gt);
+    return launch_one<MAXD, false, false, WPS, LB, F32F, BVH, TASKS, TPW, HF, SPARSE>(a, a->lds_lstack_bytes, stream, gt);
 }
 
 #ifndef RG_LIGHT_BIG_TILES
@@ -137,12 +139,21 @@ static hipError_t launch_waves(const RgKernelArgs *a, hipStream_t stream, size_t
 // fatter iterations (RG_LB shadow rays per pass) at 2 waves/SIMD.  Heavy
 // scenes: the body loop dominates and waves mix ray kinds -> one ray per
 // lane in ONE shared loop, 4 waves/SIMD to hide LDS/FP64 latency.
-template <int MAXD>
+template <int MAXD, bool SPARSE = false>
 __attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs *a, hipStream_t stream, size_t *gt) {
     // a launch on its own (not one of several frames in flight): persistent waves at full
     // occupancy balance the tiles dynamically, where a fixed tiles-per-wave grid makes every
     // wave render exactly that many tiles and the slowest wave's sum the makespan
     // (2: launches below RG_LIGHT_BIG_TILES tiles only -- rg_render_multi's shares and bands)
+    if constexpr (SPARSE) {  // MAXD == 0: one instantiation per light-batch width
+#if RG_LB_ONE
+        if (a->n_lights <= 1) return launch_waves<0, RG_LIGHT_WPS_ONE, -1, false, false, false, 0, false, true>(a, stream, gt);
+#endif
+#if RG_LB_SMALL > 1
+        if (a->n_lights <= RG_LB_SMALL) return launch_waves<0, RG_LIGHT_WPS, RG_LB_SMALL, false, false, false, 0, false, true>(a, stream, gt);
+#endif
+        return launch_waves<0, RG_LIGHT_WPS, RG_LB, false, false, false, 0, false, true>(a, stream, gt);
+    } else {
     const bool persistent = MAXD != 0 && RG_LIGHT_SINGLE_PERSISTENT && !a->pipelined &&
                             (RG_LIGHT_SINGLE_PERSISTENT != 2 || rg_tile_count(*a) < RG_LIGHT_BIG_TILES);
 #if RG_LB_ONE
@@ -174,20 +185,21 @@ __attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs
             return launch_waves<MAXD, RG_LIGHT_WPS, RG_LB, false, false, false, RG_LIGHT_TPW_BIG>(a, stream, gt);
 #endif
     return launch_waves<MAXD, RG_LIGHT_WPS, RG_LB, false, false, false>(a, stream, gt);
+    }
 }
 
-template <int MAXD, bool HF = false>
+template <int MAXD, bool HF = false, bool SPARSE = false>
 __attribute__((visibility("hidden"))) hipError_t launch_heavy(const RgKernelArgs *a, hipStream_t stream, size_t *gt) {
-    const unsigned long long tiles = rg_tile_count(*a);
+    const unsigned long long tiles = SPARSE ? a->tile_limit : rg_tile_count(*a);
     // frames in flight (pipelined): the throughput-sized grid already keeps blocks long;
     // task splitting then costs more than it saves (1/8 share 0.400 -> 0.384 ms without:
     // profiles/r02/ab_task_split.txt); a single small launch keeps it (its latency)
     const bool tasks = RG_HEAVY_TASKS && tiles < RG_HEAVY_TASK_TILES && !a->pipelined;
     if (a->n_nodes > 0)
-        return tasks ? launch_waves<MAXD, RG_HEAVY_WPS, 1, true, true, true, 0, HF>(a, stream, gt)
-                     : launch_waves<MAXD, RG_HEAVY_WPS, 1, true, true, false, 0, HF>(a, stream, gt);
-    return tasks ? launch_waves<MAXD, RG_HEAVY_WPS, 1, RG_HEAVY_F32_FILTER, false, true, 0, HF>(a, stream, gt)
-                 : launch_waves<MAXD, RG_HEAVY_WPS, 1, RG_HEAVY_F32_FILTER, false, false, 0, HF>(a, stream, gt);
+        return tasks ? launch_waves<MAXD, RG_HEAVY_WPS, 1, true, true, true, 0, HF, SPARSE>(a, stream, gt)
+                     : launch_waves<MAXD, RG_HEAVY_WPS, 1, true, true, false, 0, HF, SPARSE>(a, stream, gt);
+    return tasks ? launch_waves<MAXD, RG_HEAVY_WPS, 1, RG_HEAVY_F32_FILTER, false, true, 0, HF, SPARSE>(a, stream, gt)
+                 : launch_waves<MAXD, RG_HEAVY_WPS, 1, RG_HEAVY_F32_FILTER, false, false, 0, HF, SPARSE>(a, stream, gt);
 }
 
 // one explicit instantiation each, in the rg_render_*.hip of that name
@@ -200,3 +212,5 @@ extern template hipError_t launch_heavy<16, false>(const RgKernelArgs *, hipStre
 extern template hipError_t launch_heavy<64, false>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_heavy<0, false>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_heavy<8, true>(const RgKernelArgs *, hipStream_t, size_t *);
+extern template hipError_t launch_light<0, true>(const RgKernelArgs *, hipStream_t, size_t *);
+extern template hipError_t launch_heavy<0, false, true>(const RgKernelArgs *, hipStream_t, size_t *);

@@ -134,6 +134,50 @@ __global__ __launch_bounds__(RG_RESOLVE_BX *RG_RESOLVE_BY) void rg_resolve_kerne
     }
 }
 
+// The resolve of adaptive anti-aliasing (rg_aa.hip): per output pixel of a band, one thread.
+// A flagged pixel (mask byte non-zero, `in` non-null) is the box resolve of its k x k samples
+// in resolve_one's order and arithmetic, from the band's sample slot (only the samples of
+// flagged pixels were rendered there); an unflagged pixel keeps the base frame's bytes, and
+// its base f32 RGB is clamped in place when `rgb` is wanted (the k = 1 resolve).  Per wave:
+// 64 mask bytes read; per flagged lane k runs of 12 k B read (adjacent flagged lanes read one
+// contiguous run per sample row), 4 B (+ 12 B) written; with `rgb`, 12 B read and written per
+// unflagged lane.  Flagged pixels are a small share of the frame, so the shape is the simple one.
+struct RgAdaptArgs {
+    const float *in;      // nullable (k = 1: nothing to resolve): k rows x (k W) samples x 3 floats
+    const uint8_t *mask;  // rows x W
+    uint32_t *rgba;       // rows x W, holding the base frame
+    float *rgb;           // nullable: rows x W x 3, holding the base frame's f32 RGB
+    uint32_t W, rows, k;
+};
+
+__global__ __launch_bounds__(256) void rg_resolve_adaptive_kernel(RgAdaptArgs a) {
+    const size_t o = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (o >= (size_t)a.W * a.rows) return;
+    if (a.in && a.mask[o]) {
+        const uint32_t y = (uint32_t)(o / a.W), x = (uint32_t)(o - (size_t)y * a.W);
+        const size_t pitch = (size_t)a.W * a.k * 3;  // floats per sample row
+        const float *row = a.in + (size_t)y * a.k * pitch + (size_t)x * a.k * 3;
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        for (uint32_t j = 0; j < a.k; ++j, row += pitch)
+            for (uint32_t i = 0; i < a.k; ++i)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] = acc[c] + resolve_clamp(row[i * 3 + c]);
+        float mean[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) mean[c] = acc[c] / (float)(a.k * a.k);
+        a.rgba[o] = resolve_u8(mean[0] * 255.0f) | (resolve_u8(mean[1] * 255.0f) << 8) |
+                    (resolve_u8(mean[2] * 255.0f) << 16) | 0xFF000000u;
+        if (a.rgb) {
+            a.rgb[3 * o] = mean[0];
+            a.rgb[3 * o + 1] = mean[1];
+            a.rgb[3 * o + 2] = mean[2];
+        }
+    } else if (a.rgb) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.rgb[3 * o + c] = resolve_clamp(a.rgb[3 * o + c]);
+    }
+}
+
 template <int K>
 hipError_t launch_k(const RgResolveArgs &a, bool vin, dim3 grid, hipStream_t stream) {
     const dim3 block(RG_RESOLVE_BX, RG_RESOLVE_BY);
@@ -179,4 +223,14 @@ extern "C" hipError_t rg_launch_resolve(const float *in, uint32_t width, uint32_
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+extern "C" hipError_t rg_launch_resolve_adaptive(const float *in, const uint8_t *mask, uint32_t width, uint32_t rows,
+                                                 uint32_t k, uint8_t *rgba, float *rgb, hipStream_t stream) {
+    if (!mask || !rgba || width == 0 || k < 1 || k > 8) return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    const RgAdaptArgs a{in, mask, reinterpret_cast<uint32_t *>(rgba), rgb, width, rows, k};
+    const size_t px = (size_t)width * rows;  // < 2^32: the grid stays below 2^24 blocks
+    hipLaunchKernelGGL(rg_resolve_adaptive_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
 }

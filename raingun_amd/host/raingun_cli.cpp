@@ -2,8 +2,11 @@
 // on the native host layer (libraingun_host.so: YAML scene, textures, PNG) and
 // the HIP renderer (libraingun_hip.so: rg_render_image).
 //
-//   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [-o FILE] [--gpu N] FILE
+//   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T] [-o FILE] [--gpu N] FILE
 //
+// --adaptive T (0..256; not in the reference): the N x N rays only for pixels whose 8-neighbourhood
+// contrast in the 1-sample frame is at least T (rg_render_image_aa_adaptive); accepted with
+// --samples 1, where it has no effect.
 // --samples N (1..8, default 1; not in the reference): N x N rays per pixel on the
 // regular sub-pixel grid, box-filtered (rg_render_image_aa); --draft leaves it alone.
 // Flag semantics follow construct_app / RenderOptions::from (main.rs:21-96,
@@ -40,6 +43,7 @@ const char *kHelp =
     "        --preview    Shows render progress in a window (not available: renders without one).\n"
     "    -V, --version    Prints version information\n\n"
     "OPTIONS:\n"
+    "        --adaptive <T>         Adaptive anti-aliasing: the N x N rays only where the 1-sample frame's contrast is at least T (0..256).\n"
     "        --gpu <N>              HIP device to render on (default 0).\n"
     "    -h, --height <PIXELS>      Height of output image.\n"
     "    -o, --output <FILENAME>    Specify filename of the rendered image.\n"
@@ -61,13 +65,16 @@ const char *kHelp =
 
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
-    const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr;
+    const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr,
+               *adaptive = nullptr;
     int gpu = 0;
 };
 
 struct RenderOptions {  // render.rs:32-46
     uint32_t width = 800, height = 600;
     uint32_t samples = 1;  // N x N rays per pixel (--samples)
+    bool has_adaptive = false;
+    uint32_t adaptive = 0;  // contrast threshold (--adaptive)
     bool has_depth = false;
     uint32_t max_recursion_depth = 0;
 };
@@ -113,6 +120,7 @@ Args parse_args(int argc, char **argv) {
             else if (name == "output") a.output = take_value(i, "--output <FILENAME>", val);
             else if (name == "gpu") a.gpu = std::atoi(take_value(i, "--gpu <N>", val));
             else if (name == "samples") a.samples = take_value(i, "--samples <N>", val);
+            else if (name == "adaptive") a.adaptive = take_value(i, "--adaptive <T>", val);
             else if (val) clap_error("Found argument '" + std::string(arg) + "' which wasn't expected, or isn't valid in this context");
             else if (name == "4k") { a.uhd = true; a.hd = false; }   // overrides_with("hd")
             else if (name == "hd") { a.hd = true; a.uhd = false; }   // overrides_with("4k")
@@ -142,6 +150,12 @@ RenderOptions options_from(const Args &a) {  // main.rs:70-96
         if (!parse_u32(a.samples, &o.samples)) panic("Could not parse samples: ParseIntError { kind: InvalidDigit }");
         if (o.samples < 1 || o.samples > 8)
             clap_error(std::string("Invalid value for '--samples <N>': ") + a.samples + " is not between 1 and 8");
+    }
+    if (a.adaptive) {
+        if (!parse_u32(a.adaptive, &o.adaptive)) panic("Could not parse adaptive: ParseIntError { kind: InvalidDigit }");
+        if (o.adaptive > 256)
+            clap_error(std::string("Invalid value for '--adaptive <T>': ") + a.adaptive + " is not between 0 and 256");
+        o.has_adaptive = true;
     }
     if (a.draft) {
         o.has_depth = true;
@@ -209,7 +223,10 @@ int main(int argc, char **argv) {
     std::vector<uint8_t> rgba((size_t)opts.width * opts.height * 4);
 
     auto t0 = std::chrono::steady_clock::now();  // render.rs:54-56
-    st = opts.samples > 1 ? rg_render_image_aa(scene, opts.width, opts.height, opts.samples, rgba.data(), nullptr, nullptr)
+    st = opts.samples > 1 && opts.has_adaptive
+             ? rg_render_image_aa_adaptive(scene, opts.width, opts.height, opts.samples, opts.adaptive, rgba.data(), nullptr,
+                                           nullptr, nullptr)
+         : opts.samples > 1 ? rg_render_image_aa(scene, opts.width, opts.height, opts.samples, rgba.data(), nullptr, nullptr)
                           : rg_render_image(scene, opts.width, opts.height, rgba.data(), nullptr);
     auto t1 = std::chrono::steady_clock::now();
     if (st != RG_OK) panic(rg_status_string(st));

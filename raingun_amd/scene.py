@@ -350,6 +350,40 @@ class DeviceScene:
                    "rg_render_image_aa")
         return (out, rgb) if want_rgb else out
 
+    def render_image_aa_adaptive(self, width: int, height: int, samples: int, threshold: int, want_rgb: bool = False,
+                                 want_mask: bool = False, stats: Optional[_abi.rg_stats] = None,
+                                 out: Optional[np.ndarray] = None):
+        """rg_render_image_aa_adaptive: render_image_aa that traces the samples x samples rays only of the
+        pixels whose 8-neighbourhood contrast in the 1-sample frame is >= threshold (0..256;
+        raingun_amd/aa.py resolve_adaptive states the result).  Returns the (height, width, 4) uint8
+        frame, followed by the (height, width, 3) float32 means with want_rgb and by the
+        (height, width) uint8 mask (1 = supersampled) with want_mask."""
+        if out is None:
+            out = np.empty((height, width, 4), dtype=np.uint8)
+        assert out.shape == (height, width, 4) and out.dtype == np.uint8 and out.flags.c_contiguous
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        mask = np.empty((height, width), dtype=np.uint8) if want_mask else None
+        st = stats if stats is not None else _abi.rg_stats()
+        _abi.check(_abi.lib().rg_render_image_aa_adaptive(
+            self.handle, width, height, int(samples), int(threshold), out.ctypes.data,
+            rgb.ctypes.data if rgb is not None else None, mask.ctypes.data if mask is not None else None,
+            C.byref(st)), "rg_render_image_aa_adaptive")
+        res = (out,) + ((rgb,) if want_rgb else ()) + ((mask,) if want_mask else ())
+        return res if len(res) > 1 else out
+
+    def edge_mask(self, rgba: np.ndarray, threshold: int):
+        """rg_edge_mask on this scene's device: (H, W, 4) uint8 RGBA -> ((H, W) uint8 mask, its number
+        of ones), as aa.edge_mask computes it."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+        if rgba.ndim != 3 or rgba.shape[2] != 4 or rgba.size == 0:
+            raise ValueError("expected (height, width, 4) uint8 RGBA")
+        h, w = rgba.shape[:2]
+        mask = np.empty((h, w), dtype=np.uint8)
+        n = C.c_uint32(0)
+        _abi.check(_abi.lib().rg_edge_mask(int(self.device), rgba.ctypes.data, w, h, int(threshold), mask.ctypes.data,
+                                           C.byref(n)), "rg_edge_mask")
+        return mask, int(n.value)
+
     def resolve_box(self, rgb: np.ndarray, samples: int):
         """rg_resolve_box on this scene's device: (samples*H, samples*W, 3) float32 samples ->
         ((H, W, 3) float32 means, (H, W, 4) uint8 RGBA), as aa.resolve_box computes them."""
@@ -438,10 +472,14 @@ class Scene:                   # scene.rs:11-31
         return DeviceScene(self, device)
 
     # scene.rs:41-43 -> rendering::render_image (rendering.rs:24-38), on the GPU
-    # samples > 1: samples x samples rays per pixel, box-filtered (rg_render_image_aa)
-    def render_image(self, width: int, height: int, device: int = 0, samples: int = 1) -> np.ndarray:
+    # samples > 1: samples x samples rays per pixel, box-filtered (rg_render_image_aa);
+    # adaptive = T (0..256): only for pixels on edges of the 1-sample frame (rg_render_image_aa_adaptive)
+    def render_image(self, width: int, height: int, device: int = 0, samples: int = 1,
+                     adaptive: Optional[int] = None) -> np.ndarray:
         ds = DeviceScene(self, device)
         try:
+            if adaptive is not None:
+                return ds.render_image_aa_adaptive(width, height, samples, adaptive)
             if samples != 1:
                 return ds.render_image_aa(width, height, samples)
             return ds.render_image(width, height)
