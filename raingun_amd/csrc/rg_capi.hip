@@ -8,7 +8,9 @@
 // delivery to the caller and the stats tail of every path here in rg_bands.hip,
 // the band arithmetic in rg_band_plan.h, the pageable-frame copy pool in
 // rg_copy_pool.cpp, the single-process multi-GPU entry (rg_render_multi) in
-// rg_multi.hip, the supersampled frames (rg_render_image_aa) in rg_aa.hip.
+// rg_multi.hip (the dealing of tiles it and rg_frames.hip share in rg_tile_deal.h, their
+// pack and re-interleave kernels in rg_gather.hip, the RCCL loader in rg_rccl.hip), the
+// supersampled frames (rg_render_image_aa) in rg_aa.hip.
 // Once a path here has enqueued work that stores into the caller's buffer,
 // every error exit drains its streams first (rg_bands_drain).  No exception or
 // abort crosses the ABI.

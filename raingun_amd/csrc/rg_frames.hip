@@ -9,6 +9,9 @@
 // every rank issues and runs them in frame order; renders of consecutive frames
 // overlap on their own streams.  Host work per frame is a handful of runtime
 // calls (the Python pipeline spent ~70 us per frame on rank 0).
+// Which tiles a rank renders and how large the parts and the gather slots are is the
+// deal of rg_tile_deal.h; the pack and re-interleave kernels are in rg_gather.hip, the
+// communicators (rg_comm_*) in rg_rccl.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,99 +22,11 @@
 #include "../../include/raingun_debug.h"
 #include "../../include/raingun_frames.h"
 #include "rg_internal.h"
+#include "rg_rccl.h"
+#include "rg_tile_deal.h"
 
-namespace {
-
-// The gathered parts travel as packed RGB, 3 B per pixel: alpha is always
-// 255 (color.rs rgba()), so a quarter of every gather's bytes over xGMI carried
-// no information.  Non-root ranks pack their part after the render; the root
-// re-interleaves its OWN rows straight from its RGBA part (its slot of the
-// gather is not read) and the others' from the packed slots, re-adding alpha.
-__global__ __launch_bounds__(256) void rg_pack_rgb_kernel(const uint32_t *rgba, uint8_t *rgb, size_t npx) {
-    const size_t g = (size_t)blockIdx.x * 256u + threadIdx.x;  // pixels 4g .. 4g+3
-    const size_t p0 = g * 4u;
-    if (p0 >= npx) return;
-    if (p0 + 4u <= npx) {
-        const uint4 v = reinterpret_cast<const uint4 *>(rgba)[g];
-        uint32_t *o = reinterpret_cast<uint32_t *>(rgb + p0 * 3u);  // 12 g bytes: dword aligned
-        o[0] = (v.x & 0xFFFFFFu) | (v.y << 24);
-        o[1] = ((v.y >> 8) & 0xFFFFu) | (v.z << 16);
-        o[2] = ((v.z >> 16) & 0xFFu) | ((v.w & 0xFFFFFFu) << 8);
-    } else {
-        for (size_t p = p0; p < npx; ++p) {
-            const uint32_t v = rgba[p];
-            rgb[3 * p] = (uint8_t)v;
-            rgb[3 * p + 1] = (uint8_t)(v >> 8);
-            rgb[3 * p + 2] = (uint8_t)(v >> 16);
-        }
-    }
-}
-
-// Image row y lives in tile t = y / T.  The tiles are dealt in periods of
-// P = root + world - 1: the first `root` tiles of each period to rank 0, then one
-// to each other rank (root = 1: the round robin t -> rank t % world).  Tile t is
-// that rank's (t / P * root + t % P)-th (rank 0) or (t / P)-th tile (the others):
-// its row of the part is that index * T + y % T (distributed.py assemble).  Rank
-// 0's rows come from root_part (RGBA), the others' from their packed slots
-// (slot_bytes apart).  4 pixels per thread.
-__global__ __launch_bounds__(256) void rg_reinterleave_kernel(const uint8_t *gathered, const uint32_t *root_part,
-                                                              uint32_t *image, uint32_t width, uint32_t height,
-                                                              uint32_t tile_rows, uint32_t world, uint32_t root,
-                                                              size_t slot_bytes) {
-    const uint32_t y = blockIdx.y;
-    const uint32_t x0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
-    if (y >= height || x0 >= width) return;
-    const uint32_t t = y / tile_rows, P = root + world - 1u;
-    const uint32_t p = t / P, j = t - p * P;
-    const uint32_t r = j < root ? 0u : j - root + 1u;
-    const uint32_t src_row = (r == 0u ? p * root + j : p) * tile_rows + (y - t * tile_rows);
-    uint32_t *dst = image + (size_t)y * width + x0;
-    const size_t src_px = (size_t)src_row * width + x0;
-    if (r == 0) {
-        const uint32_t n = min(4u, width - x0);
-        for (uint32_t k = 0; k < n; ++k) dst[k] = root_part[src_px + k];
-        return;
-    }
-    const uint8_t *src = gathered + (size_t)r * slot_bytes + src_px * 3u;
-    if ((width & 3u) == 0u) {  // whole, dword-aligned groups of 4 pixels
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(src);
-        const uint32_t a = w[0], b = w[1], c = w[2];
-        uint4 o;
-        o.x = (a & 0xFFFFFFu) | 0xFF000000u;
-        o.y = (a >> 24) | ((b & 0xFFFFu) << 8) | 0xFF000000u;
-        o.z = (b >> 16) | ((c & 0xFFu) << 16) | 0xFF000000u;
-        o.w = (c >> 8) | 0xFF000000u;
-        *reinterpret_cast<uint4 *>(dst) = o;
-    } else {
-        const uint32_t n = min(4u, width - x0);
-        for (uint32_t k = 0; k < n; ++k)
-            dst[k] = (uint32_t)src[3 * k] | ((uint32_t)src[3 * k + 1] << 8) | ((uint32_t)src[3 * k + 2] << 16) |
-                     0xFF000000u;
-    }
-}
-
-}  // namespace
-
-size_t rg_packed_slot_bytes(uint32_t slot_rows, uint32_t width) {
-    return ((size_t)slot_rows * width * 3u + 15u) & ~(size_t)15u;
-}
-
-hipError_t rg_launch_pack_rgb(const void *rgba, void *rgb, size_t npx, hipStream_t stream) {
-    const size_t groups = (npx + 3u) / 4u;
-    hipLaunchKernelGGL(rg_pack_rgb_kernel, dim3((unsigned)((groups + 255u) / 256u)), dim3(256), 0, stream,
-                       static_cast<const uint32_t *>(rgba), static_cast<uint8_t *>(rgb), npx);
-    return hipGetLastError();
-}
-
-hipError_t rg_launch_reinterleave(const void *gathered, const void *root_part, void *image, uint32_t width,
-                                  uint32_t height, uint32_t tile_rows, uint32_t world, size_t slot_bytes,
-                                  hipStream_t stream, uint32_t root) {
-    dim3 grid((((width + 3u) / 4u) + 255u) / 256u, height);
-    hipLaunchKernelGGL(rg_reinterleave_kernel, grid, dim3(256), 0, stream, static_cast<const uint8_t *>(gathered),
-                       static_cast<const uint32_t *>(root_part), static_cast<uint32_t *>(image), width, height,
-                       tile_rows, world, root, slot_bytes);
-    return hipGetLastError();
-}
+// batch buffers hold the largest batch (rg_frames_set_batch); batch p = slots 2p, 2p+1
+constexpr int B = 2;
 
 struct rg_frames {
     const rg_scene *scene = nullptr;
@@ -199,9 +114,9 @@ rg_status rg_frames_create(const rg_scene *scene, uint32_t width, uint32_t heigh
     f->depth = depth;
     f->comm = comm;
     f->gather = gather;
-    f->tiling = rg_tiling{tile_rows, (uint32_t)world, (uint32_t)rank};
-    const uint32_t tiles = (height + tile_rows - 1) / tile_rows;
-    f->slot_rows = (tiles + (uint32_t)world - 1) / (uint32_t)world * tile_rows;  // equal on every rank
+    const rg_deal deal{tile_rows, (uint32_t)world, 1u};
+    f->tiling = rg_deal_tiling(deal, (uint32_t)rank);
+    f->slot_rows = rg_deal_slot_rows(deal, height);  // equal on every rank
     f->root_part_rows = f->slot_rows;
     f->part_bytes = (size_t)f->slot_rows * width * 4;
     f->slot_bytes = rg_packed_slot_bytes(f->slot_rows, width);
@@ -220,7 +135,6 @@ rg_status rg_frames_create(const rg_scene *scene, uint32_t width, uint32_t heigh
     // two frames per gather halve rank 0's per-frame enqueue cost (RCCL's host work
     // is per call); a depth that is not even keeps one
     f->batch = (world > 1 && depth % 2 == 0) ? 2 : 1;
-    const int B = 2;  // batch buffers hold the largest batch (rg_frames_set_batch); batch p = slots 2p, 2p+1
     f->render.assign(depth, nullptr);
     for (int b = 0; b < depth && good; ++b) {
         stream(f->render[b]);
@@ -256,7 +170,6 @@ namespace {
 // ONE gather for the n consecutive frames of slots b0 .. b0 + n - 1 (one batch):
 // rank r's chunk of the receive buffer holds its n packed parts back to back.
 rg_status issue_gather(rg_frames *f, int b0, int n) {
-    const int B = 2;
     const int p = b0 / B, h0 = b0 % B;  // the batch's buffers, the first frame's place in them
     const size_t count = (size_t)n * f->slot_bytes;
     void *send = f->rank == 0 ? f->parts[b0] : static_cast<uint8_t *>(f->packed[p]) + (size_t)h0 * f->slot_bytes;
@@ -264,10 +177,10 @@ rg_status issue_gather(rg_frames *f, int b0, int n) {
     // buffers (send: slot h; receive: from h0 * world slots on), so the next frames'
     // gather never overwrites what the root's re-interleave of this one still reads
     void *recv = f->rank == 0 ? static_cast<uint8_t *>(f->gathered[p]) + (size_t)h0 * f->world * f->slot_bytes : nullptr;
-    // ncclUint8 = 1 (rccl.h); recvbuff may be NULL off the root.  ncclSuccess = 0;
-    // a non-blocking communicator may answer ncclInProgress = 7 with the operation enqueued
-    const int gr = f->gather(send, recv, count, 1, 0, f->comm, f->comm_stream);
-    if (gr != 0 && gr != 7) return RG_ERR_DEVICE;
+    // recvbuff may be NULL off the root.  ncclSuccess = 0; a non-blocking communicator
+    // may answer ncclInProgress with the operation enqueued
+    const int gr = f->gather(send, recv, count, kNcclUint8, 0, f->comm, f->comm_stream);
+    if (gr != 0 && gr != kNcclInProgress) return RG_ERR_DEVICE;
     if (!ok(hipEventRecord(f->sent[b0], f->comm_stream))) return RG_ERR_DEVICE;
     if (f->rank == 0 && !ok(hipStreamWaitEvent(f->side, f->sent[b0], 0))) return RG_ERR_DEVICE;
     for (int h = 0; h < n; ++h) {
@@ -297,14 +210,11 @@ int rg_debug_gather_noop(const void *, void *, size_t, int, int, void *, void *)
 rg_status rg_frames_set_root_tiles(rg_frames *f, int32_t root_tiles) {
     if (!f || root_tiles < 1 || root_tiles > 64 || f->k != 0) return RG_ERR_INVALID_ARGUMENT;
     if (f->world == 1) return root_tiles == 1 ? RG_OK : RG_ERR_INVALID_ARGUMENT;
-    const uint32_t R = (uint32_t)root_tiles, P = R + (uint32_t)f->world - 1u;
-    // rank 0: R consecutive tiles per period; rank r > 0: tile R + r - 1 of each period
-    f->root = R;
-    f->tiling = f->rank == 0 ? rg_tiling{f->T, P, 0u} : rg_tiling{f->T, P, R + (uint32_t)f->rank - 1u};
-    const rg_tiling t1{f->T, P, R};  // rank 1 holds the most tiles of the other ranks
-    const rg_tiling t0{f->T, P, 0u};
-    const uint32_t slot_rows = rg_tiling_rows_grouped(f->h, &t1, 1);
-    const size_t root_rows = rg_tiling_rows_grouped(f->h, &t0, R);
+    const rg_deal deal{f->T, (uint32_t)f->world, (uint32_t)root_tiles};
+    f->root = deal.root;
+    f->tiling = rg_deal_tiling(deal, (uint32_t)f->rank);
+    const uint32_t slot_rows = rg_deal_slot_rows(deal, f->h);
+    const size_t root_rows = rg_deal_part_rows(deal, f->h, 0);
     const size_t part_rows = f->rank == 0 ? std::max<size_t>(root_rows, slot_rows) : slot_rows;
     if (part_rows * f->w * 4 > f->part_bytes) {  // rank 0's part grew: new part buffers
         for (void *&p : f->parts) {
@@ -341,12 +251,12 @@ rg_status rg_frames_step(rg_frames *f) {
     d.rgba = static_cast<uint8_t *>(f->parts[b]);
     d.stream = rs;
     d.pipelined = true;
-    d.tile_group = f->rank == 0 ? f->root : 1u;
+    d.tile_group = rg_deal_group({f->T, (uint32_t)f->world, f->root}, (uint32_t)f->rank);
     rg_status st = rg_launch_tiles(f->scene, d);
     if (st != RG_OK) return st;
     // off the root the part travels packed (3 B per pixel) in its batch's send buffer;
     // the root's own part is read in place
-    const int B = 2, p = b / B, h = b % B;
+    const int p = b / B, h = b % B;
     if (f->rank != 0 && !ok(rg_launch_pack_rgb(f->parts[b], static_cast<uint8_t *>(f->packed[p]) + (size_t)h * f->slot_bytes,
                                                (size_t)f->slot_rows * f->w, rs)))
         return RG_ERR_DEVICE;

@@ -2,9 +2,12 @@
 // by rg_scene.hip (scene upload, kernel arguments), rg_launch.hip (per-stream
 // launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
 // streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_frames.hip
-// (frames in flight over N processes) and rg_multi.hip (one process driving N
-// devices).  The band resource set the two kinds of host frames are built on is
-// in rg_bands.h, the band arithmetic in rg_band_plan.h.  Not part of the ABI.
+// (frames in flight over N processes), rg_multi.hip (one process driving N
+// devices), rg_gather.hip (the pack and re-interleave kernels of both) and rg_rccl.hip
+// (the run-time RCCL loader, rg_rccl.h, and the rg_comm_* functions).  The band resource
+// set the two kinds of host frames are built on is in rg_bands.h, the band arithmetic in
+// rg_band_plan.h, the dealing of tiles to ranks and devices in rg_tile_deal.h.  Not part
+// of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +22,7 @@
 #include "rg_copy_pool.h"
 #include "rg_device.h"
 #include "rg_lightbuf_ray.h"
+#include "rg_tile_deal.h"
 
 inline bool ok(hipError_t e) { return e == hipSuccess; }
 
@@ -260,10 +264,6 @@ struct rg_launch_desc {
 // ctx_out (nullable): the stream's launch context.
 rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx **ctx_out = nullptr);
 
-// Rows a tiling selects when its tiles come in groups of `group` consecutive image tiles per
-// stride (group 1: rg_tiling_rows); 0 for an invalid tiling or group (offset + group > stride).
-uint32_t rg_tiling_rows_grouped(uint32_t height, const rg_tiling *t, uint32_t group);
-
 // Ray counts and status of a counter snapshot (stats nullable).
 rg_status rg_snap_status(const unsigned long long *snap, rg_stats *stats);
 
@@ -291,7 +291,6 @@ void rg_multi_release(const rg_scene *s);
 // memory / device error), and its destruction.
 rg_launch_ctx *rg_ctx_for(const rg_scene *s, hipStream_t stream);
 void rg_ctx_destroy(rg_launch_ctx *c);
-bool rg_tiling_valid(const rg_tiling *t);
 
 // Grow-only buffers under one capacity: nothing if want <= cap; else free, null, allocate,
 // set the capacity.  RG_MEM_DEVICE: hipMalloc; RG_MEM_PINNED: hipHostMallocDefault;
@@ -323,5 +322,13 @@ uint32_t rg_host_tile_wlog(const rg_scene *s);
 void rg_image_res_release(rg_image_res &r);
 // rg_aa.hip: free the supersampled paths' resources.
 void rg_aa_res_release(rg_aa_res &r);
+
+// rg_gather.hip: pack npx RGBA pixels to RGB (3 B per pixel), as a part travels in a gather.
+hipError_t rg_launch_pack_rgb(const void *rgba, void *rgb, size_t npx, hipStream_t stream);
+// rg_gather.hip: the image from the parts of `world` ranks dealt `root` tiles of rank 0 per period
+// (rg_tile_deal.h): rank 0's RGBA part read in place, rank r's packed part at gathered + r * slot_bytes.
+hipError_t rg_launch_reinterleave(const void *gathered, const void *root_part, void *image, uint32_t width,
+                                  uint32_t height, uint32_t tile_rows, uint32_t world, size_t slot_bytes,
+                                  hipStream_t stream, uint32_t root = 1);
 
 #pragma GCC visibility pop

@@ -259,10 +259,6 @@ rg_launch_ctx *rg_ctx_for(const rg_scene *s, hipStream_t stream) {
     return c;
 }
 
-bool rg_tiling_valid(const rg_tiling *t) {
-    return t && t->tile_rows > 0 && t->tile_stride > 0 && t->tile_offset < t->tile_stride;
-}
-
 rg_status rg_grow(rg_mem kind, size_t &cap, size_t want, std::initializer_list<rg_grow_buf> bufs, bool clear_error) {
     if (want <= cap) return RG_OK;
     for (const rg_grow_buf &b : bufs)
@@ -319,15 +315,6 @@ rg_status rg_snap_status(const unsigned long long *snap, rg_stats *stats) {
         stats->error_pixel = -1;
     }
     return decode_error(snap[3], stats ? &stats->error_pixel : nullptr);
-}
-
-uint32_t rg_tiling_rows_grouped(uint32_t height, const rg_tiling *t, uint32_t group) {
-    if (!rg_tiling_valid(t) || height == 0 || group < 1 || (group > 1 && t->tile_offset + group > t->tile_stride)) return 0;
-    const uint32_t tiles = (height + t->tile_rows - 1) / t->tile_rows;
-    // per stride of image tiles: tiles offset .. offset + group - 1 (group 1: the round robin)
-    const uint32_t full = tiles / t->tile_stride, rem = tiles % t->tile_stride;
-    const uint32_t last = rem > t->tile_offset ? std::min(group, rem - t->tile_offset) : 0u;
-    return (full * group + last) * t->tile_rows;
 }
 
 extern "C" {

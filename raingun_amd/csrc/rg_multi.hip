@@ -20,110 +20,30 @@
 //                        (ncclGroupStart/End: one thread issues N ranks' calls)
 //   device 0, stream 0 : re-interleave gathered parts into the frame, then
 //                        copy the frame to the caller's host buffer
-// RCCL is loaded with dlopen, so libraingun_hip.so links no collective
-// library and shares the one already in a process (PyTorch's) if there is one.
+// RCCL is loaded at run time (rg_rccl.h).  The dealing of tiles to devices, the sizes of the
+// parts and the direct mode's bands and copies are arithmetic of rg_tile_deal.h; the pack and
+// re-interleave kernels are in rg_gather.hip.
 //
 // Stand-in (rg_debug_set_multi stand_in = 1, for tests on one GPU): every
 // "device" is the scene's device, each with its own replica, and the gather
 // goes through a stand-in with ncclGather's signature and group semantics
 // (device copies into the root's receive buffer, ordered after each rank's
 // render) -- so every N > 1 code path runs on a single GPU.
-#include <dlfcn.h>
 #include <hip/hip_runtime.h>
-#include <link.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <string>
 #include <vector>
 
 #include "../../include/raingun.h"
 #include "../../include/raingun_debug.h"
 #include "../../include/raingun_frames.h"
 #include "rg_internal.h"
-
-// rg_frames.hip: parts travel as packed RGB (3 B per pixel); device 0 reads its own part in place
-hipError_t rg_launch_reinterleave(const void *gathered, const void *root_part, void *image, uint32_t width,
-                                  uint32_t height, uint32_t tile_rows, uint32_t world, size_t slot_bytes,
-                                  hipStream_t stream, uint32_t root = 1);
-hipError_t rg_launch_pack_rgb(const void *rgba, void *rgb, size_t npx, hipStream_t stream);
-size_t rg_packed_slot_bytes(uint32_t slot_rows, uint32_t width);
+#include "rg_rccl.h"
+#include "rg_tile_deal.h"
 
 namespace {
-
-// ---------------------------------------------------------------- RCCL, loaded at run time
-typedef int (*pfn_comm_init_all)(void **comms, int ndev, const int *devlist);
-typedef int (*pfn_comm_destroy)(void *comm);
-typedef int (*pfn_gather)(const void *send, void *recv, size_t count, int dtype, int root, void *comm, hipStream_t s);
-typedef int (*pfn_group)(void);
-struct NcclUniqueId {  // ncclUniqueId (rccl.h): 128 opaque bytes, passed by value to ncclCommInitRank
-    char internal[RG_COMM_ID_BYTES];
-};
-typedef int (*pfn_get_unique_id)(NcclUniqueId *id);
-typedef int (*pfn_comm_init_rank)(void **comm, int nranks, NcclUniqueId id, int rank);
-typedef int (*pfn_comm_query)(void *comm, int *out);  // ncclCommCount / ncclCommCuDevice / ncclCommUserRank
-
-struct Rccl {
-    bool tried = false;
-    void *handle = nullptr;
-    pfn_comm_init_all init_all = nullptr;
-    pfn_comm_destroy destroy = nullptr;
-    pfn_gather gather = nullptr;
-    pfn_group group_start = nullptr, group_end = nullptr;
-    pfn_get_unique_id get_unique_id = nullptr;
-    pfn_comm_init_rank init_rank = nullptr;
-    pfn_comm_query count = nullptr, cu_device = nullptr, user_rank = nullptr;
-};
-Rccl g_rccl;
-std::mutex g_rccl_mu;
-
-int find_loaded(struct dl_phdr_info *info, size_t, void *data) {
-    if (info->dlpi_name && std::strstr(info->dlpi_name, "librccl")) {
-        *static_cast<std::string *>(data) = info->dlpi_name;
-        return 1;
-    }
-    return 0;
-}
-
-const Rccl *rccl() {
-    std::lock_guard<std::mutex> g(g_rccl_mu);
-    if (g_rccl.tried) return g_rccl.handle ? &g_rccl : nullptr;
-    g_rccl.tried = true;
-    std::string loaded;
-    dl_iterate_phdr(find_loaded, &loaded);
-    std::vector<std::string> cands;
-    if (!loaded.empty()) cands.push_back(loaded);  // the instance already in the process (e.g. PyTorch's)
-    if (const char *e = std::getenv("RG_RCCL_LIBRARY")) cands.push_back(e);
-    cands.push_back("librccl.so.1");
-    cands.push_back("/opt/rocm/lib/librccl.so.1");
-    for (const std::string &c : cands) {
-        void *h = dlopen(c.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) continue;
-        g_rccl.init_all = reinterpret_cast<pfn_comm_init_all>(dlsym(h, "ncclCommInitAll"));
-        g_rccl.destroy = reinterpret_cast<pfn_comm_destroy>(dlsym(h, "ncclCommDestroy"));
-        g_rccl.gather = reinterpret_cast<pfn_gather>(dlsym(h, "ncclGather"));
-        g_rccl.group_start = reinterpret_cast<pfn_group>(dlsym(h, "ncclGroupStart"));
-        g_rccl.group_end = reinterpret_cast<pfn_group>(dlsym(h, "ncclGroupEnd"));
-        g_rccl.get_unique_id = reinterpret_cast<pfn_get_unique_id>(dlsym(h, "ncclGetUniqueId"));
-        g_rccl.init_rank = reinterpret_cast<pfn_comm_init_rank>(dlsym(h, "ncclCommInitRank"));
-        g_rccl.count = reinterpret_cast<pfn_comm_query>(dlsym(h, "ncclCommCount"));
-        g_rccl.cu_device = reinterpret_cast<pfn_comm_query>(dlsym(h, "ncclCommCuDevice"));
-        g_rccl.user_rank = reinterpret_cast<pfn_comm_query>(dlsym(h, "ncclCommUserRank"));
-        if (g_rccl.init_all && g_rccl.destroy && g_rccl.gather && g_rccl.group_start && g_rccl.group_end &&
-            g_rccl.get_unique_id && g_rccl.init_rank && g_rccl.count && g_rccl.cu_device && g_rccl.user_rank) {
-            g_rccl.handle = h;
-            return &g_rccl;
-        }
-        dlclose(h);
-    }
-    return nullptr;
-}
-
-constexpr int kNcclUint8 = 1;       // ncclDataType_t (rccl.h)
-constexpr int kNcclInProgress = 7;  // a non-blocking communicator's "enqueued"
 
 // ---------------------------------------------------------------- stand-in gather
 // ncclGather's signature and the semantics rg_render_multi relies on: within
@@ -159,9 +79,17 @@ int stand_in_gather(const void *send, void *recv, size_t count, int dtype, int r
                : 1;
 }
 
-#ifndef RG_MULTI_BAND_PX
-#define RG_MULTI_BAND_PX (1u << 20)  // a device's share is cut into bands of about this many pixels (at most 4)
-#endif
+// One device's share of the work (value-initialised: a partly built set frees cleanly).
+struct multi_dev {
+    int device = 0;
+    rg_scene *rep = nullptr;  // dev[0]: the scene itself (not owned)
+    void *comm = nullptr;
+    hipStream_t stream = nullptr;   // render stream A (gather: the only one)
+    hipStream_t stream2 = nullptr;  // direct: render stream B (bands alternate)
+    hipStream_t copy = nullptr;     // direct: device-to-host copy stream
+    hipEvent_t ev_band[RG_MULTI_MAX_BANDS] = {}, ev_copy[RG_MULTI_MAX_BANDS] = {};  // direct: per band
+    void *part = nullptr, *packed = nullptr;  // dev[0].packed unused: device 0's part is read in place
+};
 
 }  // namespace
 
@@ -173,16 +101,9 @@ struct rg_multi_res {
     bool stand_in = false;
     size_t part_bytes = 0;   // RGBA part
     size_t slot_bytes = 0;   // packed RGB part each device sends (gather)
-    std::vector<int> devs;
-    std::vector<rg_scene *> reps;      // reps[0] = the scene itself (not owned)
-    std::vector<void *> comms;
+    std::vector<multi_dev> dev;
     std::vector<StandInComm> sic;      // stand-in communicators
     StandInGroup sig;
-    std::vector<hipStream_t> streams;  // render stream A per device (gather: the only one)
-    std::vector<hipStream_t> streams2; // direct: render stream B per device (bands alternate)
-    std::vector<hipStream_t> copies;   // direct: device-to-host copy stream per device
-    std::vector<std::vector<hipEvent_t>> ev_band, ev_copy;  // direct: per device, per band
-    std::vector<void *> parts, packed;            // packed[0] unused: device 0's part is read in place
     void *gathered = nullptr, *image = nullptr;  // device 0 (gather)
     void *h_frame = nullptr;                     // direct into pageable memory: pinned, portable frame
     unsigned long long *snap = nullptr;          // pinned: 4 words per (device, band)
@@ -191,34 +112,46 @@ struct rg_multi_res {
 
 namespace {
 
+// Every stream of every device, the devices in ascending or descending order: makes the device
+// current and calls f(stream).  False if a device could not be made current or an f said false.
+template <class F>
+bool each_stream(rg_multi_res *m, bool descending, F f) {
+    bool good = true;
+    const int n = (int)m->dev.size();
+    for (int k = 0; k < n; ++k) {
+        multi_dev &d = m->dev[descending ? n - 1 - k : k];
+        good = ok(hipSetDevice(d.device)) && good;
+        for (hipStream_t x : {d.stream, d.stream2, d.copy})
+            if (x) good = f(x) && good;
+    }
+    return good;
+}
+
+bool sync_stream(hipStream_t x) { return ok(hipStreamSynchronize(x)); }
+
 void free_res(rg_multi_res *m) {
     if (!m) return;
-    const Rccl *r = g_rccl.handle ? &g_rccl : nullptr;
-    for (int i = 0; i < (int)m->devs.size(); ++i) {
-        (void)hipSetDevice(m->devs[i]);
-        for (auto *v : {&m->streams, &m->streams2, &m->copies})
-            if (i < (int)v->size() && (*v)[i]) (void)hipStreamSynchronize((*v)[i]);
-    }
-    for (int i = 0; i < (int)m->devs.size(); ++i) {
-        (void)hipSetDevice(m->devs[i]);
-        if (!m->stand_in && i < (int)m->comms.size() && m->comms[i] && r) (void)r->destroy(m->comms[i]);
-        if (i < (int)m->parts.size() && m->parts[i]) (void)hipFree(m->parts[i]);
-        if (i < (int)m->packed.size() && m->packed[i]) (void)hipFree(m->packed[i]);
+    const Rccl *r = rccl_loaded();
+    (void)each_stream(m, false, sync_stream);
+    for (multi_dev &d : m->dev) {
+        (void)hipSetDevice(d.device);
+        if (!m->stand_in && d.comm && r) (void)r->destroy(d.comm);
+        if (d.part) (void)hipFree(d.part);
+        if (d.packed) (void)hipFree(d.packed);
         // the render streams' launch state lives in the replicas; the scene's own
-        // (reps[0]) outlives these streams, so forget it before they go
-        for (auto *v : {&m->streams, &m->streams2}) {
-            if (i >= (int)v->size() || !(*v)[i]) continue;
-            if (i < (int)m->reps.size() && m->reps[i]) (void)rg_scene_release_stream(m->reps[i], (*v)[i]);
-            (void)hipStreamDestroy((*v)[i]);
+        // (dev[0].rep) outlives these streams, so forget it before they go
+        for (hipStream_t x : {d.stream, d.stream2}) {
+            if (!x) continue;
+            if (d.rep) (void)rg_scene_release_stream(d.rep, x);
+            (void)hipStreamDestroy(x);
         }
-        if (i < (int)m->copies.size() && m->copies[i]) (void)hipStreamDestroy(m->copies[i]);
-        for (auto *v : {&m->ev_band, &m->ev_copy})
-            if (i < (int)v->size())
-                for (hipEvent_t e : (*v)[i]) if (e) (void)hipEventDestroy(e);
-        if (i > 0 && i < (int)m->reps.size() && m->reps[i]) rg_scene_free(m->reps[i]);
+        if (d.copy) (void)hipStreamDestroy(d.copy);
+        for (hipEvent_t e : d.ev_band) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : d.ev_copy) if (e) (void)hipEventDestroy(e);
+        if (&d != &m->dev[0] && d.rep) rg_scene_free(d.rep);
     }
-    if (!m->devs.empty()) {
-        (void)hipSetDevice(m->devs[0]);
+    if (!m->dev.empty()) {
+        (void)hipSetDevice(m->dev[0].device);
         if (m->gathered) (void)hipFree(m->gathered);
         if (m->image) (void)hipFree(m->image);
         if (m->ev0) (void)hipEventDestroy(m->ev0);
@@ -230,25 +163,12 @@ void free_res(rg_multi_res *m) {
     delete m;
 }
 
-constexpr int kMaxBands = 4;
-
 // Wait for everything a call enqueued on any device (render, copy streams).  An
 // error exit from the band loop may leave earlier bands' copies into the
 // caller's buffer in flight: they must land before the call returns.
 void drain(rg_multi_res *m) {
-    for (int i = 0; i < (int)m->devs.size(); ++i) {
-        (void)hipSetDevice(m->devs[i]);
-        for (auto *v : {&m->streams, &m->streams2, &m->copies})
-            if (i < (int)v->size() && (*v)[i]) (void)hipStreamSynchronize((*v)[i]);
-    }
+    (void)each_stream(m, false, sync_stream);
     (void)hipGetLastError();
-}
-
-// Bands of a device's share (direct mode): K bands of J selected tiles each.
-int multi_bands(const rg_scene *s, uint32_t W, uint32_t H, int n) {
-    if (s->multi_bands > 0) return std::min(s->multi_bands, kMaxBands);
-    const size_t share = ((size_t)W * H + (size_t)n - 1) / (size_t)n;
-    return (int)std::max<size_t>(1, std::min<size_t>(kMaxBands, share / RG_MULTI_BAND_PX));
 }
 
 rg_status build_res(const rg_scene *s, int n, uint32_t W, uint32_t H, uint32_t T, rg_multi_res **out) {
@@ -267,47 +187,38 @@ rg_status build_res(const rg_scene *s, int n, uint32_t W, uint32_t H, uint32_t T
     m->T = T;
     m->mode = mode;
     m->stand_in = stand_in;
-    const uint32_t tiles = (H + T - 1) / T;
-    m->slot_rows = (tiles + (uint32_t)n - 1) / (uint32_t)n * T;  // equal on every device
+    m->slot_rows = rg_deal_slot_rows({T, (uint32_t)n, 1u}, H);  // equal on every device
     m->part_bytes = (size_t)m->slot_rows * W * 4;
     m->slot_bytes = rg_packed_slot_bytes(m->slot_rows, W);
-    for (int i = 0; i < n; ++i) m->devs.push_back(stand_in ? s->device : (s->device + i) % ndev);
-    m->reps.assign(n, nullptr);
-    m->comms.assign(n, nullptr);
-    m->streams.assign(n, nullptr);
-    m->parts.assign(n, nullptr);
-    m->packed.assign(n, nullptr);
-    if (mode == 0) {
-        m->streams2.assign(n, nullptr);
-        m->copies.assign(n, nullptr);
-        m->ev_band.assign(n, std::vector<hipEvent_t>(kMaxBands, nullptr));
-        m->ev_copy.assign(n, std::vector<hipEvent_t>(kMaxBands, nullptr));
-    }
-    m->reps[0] = const_cast<rg_scene *>(s);
+    m->dev.resize(n);
+    for (int i = 0; i < n; ++i) m->dev[i].device = stand_in ? s->device : (s->device + i) % ndev;
+    m->dev[0].rep = const_cast<rg_scene *>(s);
     rg_status st = RG_OK;
-    for (int i = 1; i < n && st == RG_OK; ++i) st = rg_scene_replica(s, m->devs[i], &m->reps[i]);
+    for (int i = 1; i < n && st == RG_OK; ++i) st = rg_scene_replica(s, m->dev[i].device, &m->dev[i].rep);
     auto mk_stream = [](hipStream_t &x) { return ok(hipStreamCreateWithFlags(&x, hipStreamNonBlocking)); };
     for (int i = 0; i < n && st == RG_OK; ++i) {
-        if (!ok(hipSetDevice(m->devs[i])) || !mk_stream(m->streams[i]))
+        multi_dev &d = m->dev[i];
+        if (!ok(hipSetDevice(d.device)) || !mk_stream(d.stream))
             st = RG_ERR_DEVICE;
-        else if (!ok(hipMalloc(&m->parts[i], std::max(m->part_bytes, m->slot_bytes))) ||
-                 !ok(hipMemset(m->parts[i], 0, std::max(m->part_bytes, m->slot_bytes))) ||
-                 (mode == 1 && i > 0 && !ok(hipMalloc(&m->packed[i], m->slot_bytes))))
+        else if (!ok(hipMalloc(&d.part, std::max(m->part_bytes, m->slot_bytes))) ||
+                 !ok(hipMemset(d.part, 0, std::max(m->part_bytes, m->slot_bytes))) ||
+                 (mode == 1 && i > 0 && !ok(hipMalloc(&d.packed, m->slot_bytes))))
             st = RG_ERR_OUT_OF_MEMORY;  // padding rows of the last tiles stay zero
         if (st == RG_OK && mode == 0) {
-            if (!mk_stream(m->streams2[i]) || !mk_stream(m->copies[i])) st = RG_ERR_DEVICE;
-            for (int b = 0; b < kMaxBands && st == RG_OK; ++b)
-                if (!ok(hipEventCreateWithFlags(&m->ev_band[i][b], hipEventDisableTiming)) ||
-                    !ok(hipEventCreateWithFlags(&m->ev_copy[i][b], hipEventDisableTiming)))
+            if (!mk_stream(d.stream2) || !mk_stream(d.copy)) st = RG_ERR_DEVICE;
+            for (int b = 0; b < RG_MULTI_MAX_BANDS && st == RG_OK; ++b)
+                if (!ok(hipEventCreateWithFlags(&d.ev_band[b], hipEventDisableTiming)) ||
+                    !ok(hipEventCreateWithFlags(&d.ev_copy[b], hipEventDisableTiming)))
                     st = RG_ERR_DEVICE;
         }
     }
     if (st == RG_OK) {
         void *snap = nullptr;
-        (void)hipSetDevice(m->devs[0]);
+        (void)hipSetDevice(m->dev[0].device);
         if ((mode == 1 && (!ok(hipMalloc(&m->gathered, m->slot_bytes * (size_t)n)) ||
                            !ok(hipMalloc(&m->image, (size_t)H * W * 4)))) ||
-            !ok(hipHostMalloc(&snap, (size_t)n * kMaxBands * 4 * sizeof(unsigned long long), hipHostMallocPortable)))
+            !ok(hipHostMalloc(&snap, (size_t)n * RG_MULTI_MAX_BANDS * 4 * sizeof(unsigned long long),
+                              hipHostMallocPortable)))
             st = RG_ERR_OUT_OF_MEMORY;
         m->snap = static_cast<unsigned long long *>(snap);
         if (st == RG_OK && (!ok(hipEventCreate(&m->ev0)) || !ok(hipEventCreate(&m->ev1)))) st = RG_ERR_DEVICE;
@@ -318,12 +229,17 @@ rg_status build_res(const rg_scene *s, int n, uint32_t W, uint32_t H, uint32_t T
             m->sig.ev.assign(n, nullptr);
             for (int i = 0; i < n && st == RG_OK; ++i) {
                 m->sic[i] = StandInComm{i, &m->sig};
-                m->comms[i] = &m->sic[i];
+                m->dev[i].comm = &m->sic[i];
                 if (!ok(hipEventCreateWithFlags(&m->sig.ev[i], hipEventDisableTiming))) st = RG_ERR_DEVICE;
             }
-        } else if (r->init_all(m->comms.data(), n, m->devs.data()) != 0) {
-            for (void *&c : m->comms) c = nullptr;  // not (fully) created
-            st = RG_ERR_COLLECTIVE;
+        } else {
+            std::vector<void *> comms(n, nullptr);  // ncclCommInitAll takes arrays
+            std::vector<int> devs(n);
+            for (int i = 0; i < n; ++i) devs[i] = m->dev[i].device;
+            if (r->init_all(comms.data(), n, devs.data()) != 0)
+                st = RG_ERR_COLLECTIVE;  // not (fully) created: none is kept
+            else
+                for (int i = 0; i < n; ++i) m->dev[i].comm = comms[i];
         }
     }
     if (st != RG_OK) {
@@ -350,19 +266,19 @@ rg_status merge_snaps(const rg_multi_res *m, int per_dev, rg_stats *stats) {
     const rg_status err = rg_snap_status(w4, &es);
     total.error_pixel = es.error_pixel;
     float ms = 0.0f;
-    (void)hipSetDevice(m->devs[0]);
+    (void)hipSetDevice(m->dev[0].device);
     (void)hipEventElapsedTime(&ms, m->ev0, m->ev1);
     total.kernel_ms = ms;
     if (stats) *stats = total;
     return err;
 }
 
-// A launch of device i's share of the frame: tile_rows-row tiles dealt round-robin, tile t -> device t % n.
+// A launch of device i's share of the frame: its tiles of the round-robin deal (rg_tile_deal.h).
 rg_launch_desc share_launch(const rg_multi_res *m, int i, void *rgba, hipStream_t stream, unsigned long long *snap) {
     rg_launch_desc d;
     d.width = m->w;
     d.height = m->h;
-    d.tiling = {m->T, (uint32_t)m->n, (uint32_t)i};
+    d.tiling = rg_deal_tiling({m->T, (uint32_t)m->n, 1u}, (uint32_t)i);
     d.rgba = static_cast<uint8_t *>(rgba);
     d.stream = stream;
     d.snap = snap;
@@ -373,11 +289,13 @@ rg_launch_desc share_launch(const rg_multi_res *m, int i, void *rgba, hipStream_
 rg_status render_gather(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, rg_stats *stats) {
     const uint32_t W = m->w, H = m->h, T = m->T;
     const int n = m->n;
-    if (!ok(hipSetDevice(m->devs[0])) || !ok(hipEventRecord(m->ev0, m->streams[0]))) return RG_ERR_DEVICE;
+    multi_dev &d0 = m->dev[0];
+    if (!ok(hipSetDevice(d0.device)) || !ok(hipEventRecord(m->ev0, d0.stream))) return RG_ERR_DEVICE;
     for (int i = 0; i < n; ++i) {
-        rg_status st = rg_launch_tiles(m->reps[i], share_launch(m, i, m->parts[i], m->streams[i], m->snap + 4 * i));
+        multi_dev &d = m->dev[i];
+        rg_status st = rg_launch_tiles(d.rep, share_launch(m, i, d.part, d.stream, m->snap + 4 * i));
         if (st != RG_OK) return st;
-        if (i > 0 && !ok(rg_launch_pack_rgb(m->parts[i], m->packed[i], (size_t)m->slot_rows * W, m->streams[i])))
+        if (i > 0 && !ok(rg_launch_pack_rgb(d.part, d.packed, (size_t)m->slot_rows * W, d.stream)))
             return RG_ERR_DEVICE;
     }
     // one gather of the equal-size parts to device 0 (all ranks' calls in one group)
@@ -386,22 +304,22 @@ rg_status render_gather(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
     if (r && r->group_start() != 0) return RG_ERR_COLLECTIVE;
     int gerr = 0;
     for (int i = 0; i < n; ++i) {
-        (void)hipSetDevice(m->devs[i]);
-        const int g = gather(i == 0 ? m->parts[i] : m->packed[i], i == 0 ? m->gathered : nullptr, m->slot_bytes,
-                             kNcclUint8, 0, m->comms[i], m->streams[i]);
+        multi_dev &d = m->dev[i];
+        (void)hipSetDevice(d.device);
+        const int g = gather(i == 0 ? d.part : d.packed, i == 0 ? m->gathered : nullptr, m->slot_bytes, kNcclUint8, 0,
+                             d.comm, d.stream);
         if (g != 0 && g != kNcclInProgress && gerr == 0) gerr = g;
     }
     const int ge = r ? r->group_end() : 0;
     if (gerr != 0 || (ge != 0 && ge != kNcclInProgress)) return RG_ERR_COLLECTIVE;
     // device 0: re-interleave, copy to the host
-    if (!ok(hipSetDevice(m->devs[0])) ||
-        !ok(rg_launch_reinterleave(m->gathered, m->parts[0], m->image, W, H, T, (uint32_t)n, m->slot_bytes,
-                                   m->streams[0])) ||
-        !ok(hipEventRecord(m->ev1, m->streams[0])) ||
-        !ok(hipMemcpyAsync(rgba_out, m->image, (size_t)H * W * 4, hipMemcpyDeviceToHost, m->streams[0])))
+    if (!ok(hipSetDevice(d0.device)) ||
+        !ok(rg_launch_reinterleave(m->gathered, d0.part, m->image, W, H, T, (uint32_t)n, m->slot_bytes, d0.stream)) ||
+        !ok(hipEventRecord(m->ev1, d0.stream)) ||
+        !ok(hipMemcpyAsync(rgba_out, m->image, (size_t)H * W * 4, hipMemcpyDeviceToHost, d0.stream)))
         return RG_ERR_DEVICE;
     for (int i = n - 1; i >= 0; --i)
-        if (!ok(hipSetDevice(m->devs[i])) || !ok(hipStreamSynchronize(m->streams[i]))) return RG_ERR_DEVICE;
+        if (!ok(hipSetDevice(m->dev[i].device)) || !ok(hipStreamSynchronize(m->dev[i].stream))) return RG_ERR_DEVICE;
     return merge_snaps(m, 1, stats);
 }
 
@@ -415,35 +333,36 @@ rg_status render_direct_one(const rg_scene *s, rg_multi_res *m, uint8_t *dst, rg
     const int n = m->n;
     const size_t frame_bytes = (size_t)m->h * m->w * 4;
     const uint32_t wl = rg_host_tile_wlog(s);
-    if (!ok(hipSetDevice(m->devs[0])) || !ok(hipEventRecord(m->ev0, m->streams[0]))) return RG_ERR_DEVICE;
+    multi_dev &d0 = m->dev[0];
+    if (!ok(hipSetDevice(d0.device)) || !ok(hipEventRecord(m->ev0, d0.stream))) return RG_ERR_DEVICE;
     for (int i = 0; i < n; ++i) {
         unsigned long long *snap = m->snap + 4 * i;
         if (s->multi_only_rank >= 0 && i != s->multi_only_rank) {  // timeline rehearsal of one device
             std::memset(snap, 0, 4 * sizeof(unsigned long long));
             continue;
         }
-        if (!ok(hipSetDevice(m->devs[i]))) return RG_ERR_DEVICE;
+        if (!ok(hipSetDevice(m->dev[i].device))) return RG_ERR_DEVICE;
         void *d = rg_host_device_ptr(dst, frame_bytes);  // registered portable: mapped on every device
         if (!d) return RG_ERR_DEVICE;
-        rg_launch_desc ld = share_launch(m, i, d, m->streams[i], snap);
+        rg_launch_desc ld = share_launch(m, i, d, m->dev[i].stream, snap);
         ld.tile_wlog = wl;
         ld.host_frame = true;
         ld.image_rows = true;
-        const rg_status st = rg_launch_tiles(m->reps[i], ld);
+        const rg_status st = rg_launch_tiles(m->dev[i].rep, ld);
         if (st != RG_OK) return st;
     }
-    (void)hipSetDevice(m->devs[0]);
-    if (!ok(hipEventRecord(m->ev1, m->streams[0]))) return RG_ERR_DEVICE;
+    (void)hipSetDevice(d0.device);
+    if (!ok(hipEventRecord(m->ev1, d0.stream))) return RG_ERR_DEVICE;
     for (int i = n - 1; i >= 0; --i)
-        if (!ok(hipSetDevice(m->devs[i])) || !ok(hipStreamSynchronize(m->streams[i]))) return RG_ERR_DEVICE;
+        if (!ok(hipSetDevice(m->dev[i].device)) || !ok(hipStreamSynchronize(m->dev[i].stream))) return RG_ERR_DEVICE;
     return merge_snaps(m, 1, stats);
 }
 
 // Is the page-locked frame mapped into every device's address space (a buffer the
 // library registered is portable; one pinned elsewhere may be mapped on its own device only)?
 bool mapped_on_all(const rg_multi_res *m, uint8_t *dst, size_t bytes) {
-    for (int i = 0; i < m->n; ++i)
-        if (!ok(hipSetDevice(m->devs[i])) || rg_host_device_ptr(dst, bytes) == nullptr) {
+    for (const multi_dev &d : m->dev)
+        if (!ok(hipSetDevice(d.device)) || rg_host_device_ptr(dst, bytes) == nullptr) {
             (void)hipGetLastError();
             return false;
         }
@@ -451,7 +370,8 @@ bool mapped_on_all(const rg_multi_res *m, uint8_t *dst, size_t bytes) {
 }
 
 // Direct path: every device renders its tiles in K bands and copies each band
-// straight to its image rows in page-locked host memory over its own link.
+// straight to its image rows in page-locked host memory over its own link
+// (the bands and the copies' rows: rg_multi_band_plan, rg_tile_deal.h).
 rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, rg_stats *stats) {
     const uint32_t W = m->w, H = m->h, T = m->T;
     const int n = m->n;
@@ -469,9 +389,10 @@ rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
     if (!pageable && (s->multi_bands < 0 || (s->multi_bands == 0 && (s->multi_light_one || rg_scene_heavy(s)))) &&
         mapped_on_all(m, dst, frame_bytes))
         return render_direct_one(s, m, dst, stats);
+    multi_dev &d0 = m->dev[0];
     if (pageable) {
         if (!m->h_frame) {
-            (void)hipSetDevice(m->devs[0]);
+            (void)hipSetDevice(d0.device);
             if (!ok(hipHostMalloc(&m->h_frame, frame_bytes, hipHostMallocPortable))) {
                 (void)hipGetLastError();
                 m->h_frame = nullptr;
@@ -480,72 +401,60 @@ rg_status render_direct(const rg_scene *s, rg_multi_res *m, uint8_t *rgba_out, r
         }
         dst = static_cast<uint8_t *>(m->h_frame);
     }
-    const uint32_t tiles = (H + T - 1) / T;
-    const uint32_t per_dev = (tiles + (uint32_t)n - 1) / (uint32_t)n;  // selected tiles of device 0 (the most)
-    const uint32_t J = (per_dev + (uint32_t)multi_bands(s, W, H, n) - 1) / (uint32_t)multi_bands(s, W, H, n);
-    const int K = (int)((per_dev + J - 1) / J);  // bands of J tiles per device (device 0's are all non-empty)
-    if (!ok(hipSetDevice(m->devs[0])) || !ok(hipEventRecord(m->ev0, m->streams[0]))) return RG_ERR_DEVICE;
+    const rg_multi_plan plan = rg_multi_band_plan(W, H, T, n, s->multi_bands);
+    const int K = plan.K;
+    if (!ok(hipSetDevice(d0.device)) || !ok(hipEventRecord(m->ev0, d0.stream))) return RG_ERR_DEVICE;
     for (int b = 0; b < K; ++b) {
         for (int i = 0; i < n; ++i) {
-            const uint32_t sel = (tiles > (uint32_t)i) ? (tiles - (uint32_t)i + (uint32_t)n - 1) / (uint32_t)n : 0u;
-            uint32_t j0 = std::min(sel, (uint32_t)b * J), j1 = std::min(sel, j0 + J);
-            if (s->multi_only_rank >= 0 && i != s->multi_only_rank) j1 = j0;  // timeline rehearsal of one device
+            multi_dev &d = m->dev[i];
+            rg_multi_band c = rg_multi_band_of(plan, (uint32_t)i, (uint32_t)b);
+            if (s->multi_only_rank >= 0 && i != s->multi_only_rank) c.j1 = c.j0;  // timeline rehearsal of one device
             unsigned long long *snap = m->snap + 4 * ((size_t)i * K + b);
-            if (!ok(hipSetDevice(m->devs[i]))) return RG_ERR_DEVICE;
-            hipStream_t rs = (b & 1) ? m->streams2[i] : m->streams[i];
+            if (!ok(hipSetDevice(d.device))) return RG_ERR_DEVICE;
+            hipStream_t rs = (b & 1) ? d.stream2 : d.stream;
             if (b == 1 && i == 0 && !ok(hipStreamWaitEvent(rs, m->ev0, 0))) return RG_ERR_DEVICE;
-            if (j1 == j0) {  // nothing of this device in this band
+            if (c.j1 == c.j0) {  // nothing of this device in this band
                 std::memset(snap, 0, 4 * sizeof(unsigned long long));
-                if (!ok(hipEventRecord(m->ev_copy[i][b], m->copies[i]))) return RG_ERR_DEVICE;
+                if (!ok(hipEventRecord(d.ev_copy[b], d.copy))) return RG_ERR_DEVICE;
                 continue;
             }
-            uint8_t *part = static_cast<uint8_t *>(m->parts[i]) + (size_t)j0 * T * row4;
+            uint8_t *part = static_cast<uint8_t *>(d.part) + (size_t)c.j0 * T * row4;
             rg_launch_desc ld = share_launch(m, i, part, rs, snap);
-            ld.tile_first = j0;
-            ld.tile_count = j1 - j0;
-            rg_status st = rg_launch_tiles(m->reps[i], ld);
+            ld.tile_first = c.j0;
+            ld.tile_count = c.j1 - c.j0;
+            rg_status st = rg_launch_tiles(d.rep, ld);
             if (st != RG_OK) return st;
-            if (!ok(hipEventRecord(m->ev_band[i][b], rs)) || !ok(hipStreamWaitEvent(m->copies[i], m->ev_band[i][b], 0)))
+            if (!ok(hipEventRecord(d.ev_band[b], rs)) || !ok(hipStreamWaitEvent(d.copy, d.ev_band[b], 0)))
                 return RG_ERR_DEVICE;
-            // selected tile j of device i is image tile j*n + i: whole tiles in one strided
-            // copy, the image's last (partial) tile, if it is this device's, on its own
-            const uint32_t last_j = (tiles - 1u - (uint32_t)i) / (uint32_t)n;  // valid: sel > 0
-            const bool has_partial = (tiles - 1u) % (uint32_t)n == (uint32_t)i && j1 - 1 == last_j && H % T != 0;
-            const uint32_t full = (j1 - j0) - (has_partial ? 1u : 0u);
-            uint8_t *d0 = dst + ((size_t)j0 * n + (size_t)i) * T * row4;
-            if (full > 0 && !ok(hipMemcpy2DAsync(d0, (size_t)n * T * row4, part, (size_t)T * row4, (size_t)T * row4,
-                                                 full, hipMemcpyDeviceToHost, m->copies[i])))
+            // whole tiles in one strided copy, the image's last (partial) tile, if it is this
+            // band's, on its own
+            if (c.full > 0 && !ok(hipMemcpy2DAsync(dst + c.dst_row * row4, (size_t)n * T * row4, part, (size_t)T * row4,
+                                                   (size_t)T * row4, c.full, hipMemcpyDeviceToHost, d.copy)))
                 return RG_ERR_DEVICE;
-            if (has_partial) {
-                const uint32_t y0 = (tiles - 1u) * T;
-                if (!ok(hipMemcpyAsync(dst + (size_t)y0 * row4, part + (size_t)full * T * row4, (size_t)(H - y0) * row4,
-                                       hipMemcpyDeviceToHost, m->copies[i])))
-                    return RG_ERR_DEVICE;
-            }
-            if (!ok(hipEventRecord(m->ev_copy[i][b], m->copies[i]))) return RG_ERR_DEVICE;
+            if (c.has_partial &&
+                !ok(hipMemcpyAsync(dst + c.partial_row * row4, part + (size_t)c.full * T * row4, c.partial_rows * row4,
+                                   hipMemcpyDeviceToHost, d.copy)))
+                return RG_ERR_DEVICE;
+            if (!ok(hipEventRecord(d.ev_copy[b], d.copy))) return RG_ERR_DEVICE;
         }
     }
     // kernel_ms: device 0's renders (its last band on the second stream joined)
-    (void)hipSetDevice(m->devs[0]);
-    const int last_b = (K - 1) & 1 ? K - 1 : K - 2;  // last band on streams2 (odd index), -1: none
-    if (last_b > 0 && !ok(hipStreamWaitEvent(m->streams[0], m->ev_band[0][last_b], 0))) return RG_ERR_DEVICE;
-    if (!ok(hipEventRecord(m->ev1, m->streams[0]))) return RG_ERR_DEVICE;
+    (void)hipSetDevice(d0.device);
+    const int last_b = (K - 1) & 1 ? K - 1 : K - 2;  // last band on stream2 (odd index), -1: none
+    if (last_b > 0 && !ok(hipStreamWaitEvent(d0.stream, d0.ev_band[last_b], 0))) return RG_ERR_DEVICE;
+    if (!ok(hipEventRecord(m->ev1, d0.stream))) return RG_ERR_DEVICE;
     if (pageable) {
-        // band b's image rows [b J n T, (b + 1) J n T) are complete once every device copied its part
+        // band b's image rows are complete once every device copied its part
         rg_copy_pool &pool = rg_bands_pool(s->img);
         rg_copy_pool::Active active(pool);
         for (int b = 0; b < K; ++b) {
-            for (int i = 0; i < n; ++i)
-                if (!ok(hipSetDevice(m->devs[i])) || !ok(hipEventSynchronize(m->ev_copy[i][b]))) return RG_ERR_DEVICE;
-            const size_t y0 = std::min<size_t>(H, (size_t)b * J * n * T), y1 = std::min<size_t>(H, (size_t)(b + 1) * J * n * T);
-            if (y1 > y0) pool.copy(rgba_out + y0 * row4, dst + y0 * row4, (y1 - y0) * row4);
+            for (const multi_dev &d : m->dev)
+                if (!ok(hipSetDevice(d.device)) || !ok(hipEventSynchronize(d.ev_copy[b]))) return RG_ERR_DEVICE;
+            const rg_row_range y = rg_multi_band_rows(plan, (uint32_t)b);
+            if (y.y1 > y.y0) pool.copy(rgba_out + y.y0 * row4, dst + y.y0 * row4, (y.y1 - y.y0) * row4);
         }
     }
-    for (int i = n - 1; i >= 0; --i) {
-        if (!ok(hipSetDevice(m->devs[i]))) return RG_ERR_DEVICE;
-        for (hipStream_t x : {m->streams[i], m->streams2[i], m->copies[i]})
-            if (!ok(hipStreamSynchronize(x))) return RG_ERR_DEVICE;
-    }
+    if (!each_stream(m, true, sync_stream)) return RG_ERR_DEVICE;
     return merge_snaps(m, K, stats);
 }
 
@@ -575,7 +484,7 @@ extern "C" rg_status rg_render_multi(const rg_scene *s, uint32_t W, uint32_t H, 
         }
         s->multi = m;
     }
-    for (int i = 1; i < m->n; ++i) rg_sync_settings(m->reps[i], s);
+    for (int i = 1; i < m->n; ++i) rg_sync_settings(m->dev[i].rep, s);
     const rg_status st = m->mode == 1 ? render_gather(s, m, rgba_out, stats) : render_direct(s, m, rgba_out, stats);
     if (st != RG_OK) drain(m);  // no copy into rgba_out may outlive the call
     (void)hipSetDevice(s->device);
@@ -584,7 +493,7 @@ extern "C" rg_status rg_render_multi(const rg_scene *s, uint32_t W, uint32_t H, 
 
 extern "C" rg_status rg_debug_set_multi(rg_scene *s, int32_t mode, int32_t stand_in, int32_t bands,
                                         int32_t only_rank) {
-    if (!s || mode < 0 || mode > 1 || bands < -1 || bands > kMaxBands || only_rank < -1) return RG_ERR_INVALID_ARGUMENT;
+    if (!s || mode < 0 || mode > 1 || bands < -1 || bands > RG_MULTI_MAX_BANDS || only_rank < -1) return RG_ERR_INVALID_ARGUMENT;
     if (only_rank >= 0 && (mode != 0 || !stand_in)) return RG_ERR_INVALID_ARGUMENT;
     s->multi_mode = mode;
     s->multi_stand_in = stand_in != 0;
@@ -592,65 +501,3 @@ extern "C" rg_status rg_debug_set_multi(rg_scene *s, int32_t mode, int32_t stand
     s->multi_only_rank = only_rank;
     return RG_OK;
 }
-
-// ---------------------------------------------------------------- communicators of N processes
-// (include/raingun_frames.h): the library's own RCCL communicator for the
-// one-process-per-GPU frame loop -- rank 0 makes the unique id, the caller
-// hands it to every rank (any channel: torch.distributed's store, MPI, a file),
-// and every rank joins with ncclCommInitRank on its device.  No torch internals.
-extern "C" {
-
-int32_t rg_comm_id_bytes(void) { return RG_COMM_ID_BYTES; }
-
-rg_status rg_comm_unique_id(uint8_t *id) {
-    if (!id) return RG_ERR_INVALID_ARGUMENT;
-    const Rccl *r = rccl();
-    if (!r) return RG_ERR_COLLECTIVE;
-    NcclUniqueId u;
-    if (r->get_unique_id(&u) != 0) return RG_ERR_COLLECTIVE;
-    std::memcpy(id, u.internal, sizeof u.internal);
-    return RG_OK;
-}
-
-rg_status rg_comm_init_rank(const uint8_t *id, int32_t world, int32_t rank, int32_t device, void **comm) {
-    if (!comm) return RG_ERR_INVALID_ARGUMENT;
-    *comm = nullptr;
-    if (!id || world < 1 || rank < 0 || rank >= world || device < 0) return RG_ERR_INVALID_ARGUMENT;
-    const Rccl *r = rccl();
-    if (!r) return RG_ERR_COLLECTIVE;
-    int ndev = 0;
-    if (!ok(hipGetDeviceCount(&ndev)) || device >= ndev) return RG_ERR_INVALID_ARGUMENT;
-    if (!ok(hipSetDevice(device))) return RG_ERR_DEVICE;  // ncclCommInitRank binds the current device
-    NcclUniqueId u;
-    std::memcpy(u.internal, id, sizeof u.internal);
-    void *c = nullptr;
-    if (r->init_rank(&c, world, u, rank) != 0 || !c) return RG_ERR_COLLECTIVE;
-    *comm = c;
-    return RG_OK;
-}
-
-rg_status rg_comm_info(void *comm, int32_t *nranks, int32_t *rank, int32_t *device) {
-    const Rccl *r = g_rccl.handle ? &g_rccl : nullptr;
-    if (!comm || !r) return RG_ERR_INVALID_ARGUMENT;
-    const std::pair<pfn_comm_query, int32_t *> q[3] = {{r->count, nranks}, {r->user_rank, rank}, {r->cu_device, device}};
-    for (const auto &e : q) {
-        int v = 0;
-        if (!e.second) continue;
-        if (e.first(comm, &v) != 0) return RG_ERR_COLLECTIVE;
-        *e.second = v;
-    }
-    return RG_OK;
-}
-
-rg_status rg_comm_destroy(void *comm) {
-    const Rccl *r = g_rccl.handle ? &g_rccl : nullptr;
-    if (!comm || !r) return RG_ERR_INVALID_ARGUMENT;
-    return r->destroy(comm) == 0 ? RG_OK : RG_ERR_COLLECTIVE;
-}
-
-rg_gather_fn rg_comm_gather_fn(void) {
-    const Rccl *r = rccl();
-    return r ? reinterpret_cast<rg_gather_fn>(r->gather) : nullptr;
-}
-
-}  // extern "C"

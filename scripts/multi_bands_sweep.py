@@ -1,6 +1,8 @@
 """rg_render_multi's 8-device rehearsal (bench.py multi_rehearsal) for several band
 counts per device share (rg_debug_set_multi bands: -1 = one launch writing the
-caller's pinned frame, 0 = automatic, K > 0 = K bands with per-band copies).
+caller's pinned frame, 0 = automatic, K > 0 = K bands with per-band copies; the
+automatic count, RG_MULTI_BAND_PX and the cap RG_MULTI_MAX_BANDS are in
+raingun_amd/csrc/rg_tile_deal.h, rg_multi_band_plan).
     python scripts/multi_bands_sweep.py [workload ...]   -> JSON lines"""
 import json
 import sys

@@ -110,7 +110,7 @@ def test_native_pipeline_world_n_reinterleave(example_scenes, world, w, h, T, de
     ref = ds.render_image(w, h)
     lib = _abi.lib()
     slot = rd.root_slot_rows(h, world, T, root)
-    slot_bytes = (slot * w * 3 + 15) // 16 * 16  # off the root a part travels as packed RGB (rg_frames.hip)
+    slot_bytes = (slot * w * 3 + 15) // 16 * 16  # off the root a part travels as packed RGB (rg_tile_deal.h)
     parts = [torch.zeros((max(slot, 8), w, 4), dtype=torch.uint8, device="cuda") for _ in range(world)]
     others = [torch.zeros(slot_bytes, dtype=torch.uint8, device="cuda") for _ in range(world)]
     for r in range(1, world):
