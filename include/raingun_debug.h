@@ -143,6 +143,12 @@ rg_status rg_debug_counters(const rg_scene *scene, uint64_t out[16]);
  * diagnostic builds' extra statistics, e.g. -DRG_REGION_STATS region visits at 144.. */
 rg_status rg_debug_counter_words(const rg_scene *scene, int32_t first, int32_t n, uint64_t *out);
 
+/* Which light kernel the scene's latest render launch ran: *plain = 1 for the PLAIN instantiation
+ * (device-resident light launches of scenes with no disks and no boxes, no f32 RGB output, no
+ * tile order, no NaN-scene path and 1..3 lights: those facts are compiled in), 0 for any other
+ * kernel.  A word the launcher writes; results are identical either way. */
+rg_status rg_debug_last_plain(const rg_scene *scene, int32_t *plain);
+
 #ifdef __cplusplus
 }
 #endif

@@ -542,6 +542,12 @@ rg_status rg_debug_counters(const rg_scene *s, uint64_t out[16]) {
     return RG_OK;
 }
 
+rg_status rg_debug_last_plain(const rg_scene *s, int32_t *plain) {
+    if (!s || !plain || !s->last) return RG_ERR_INVALID_ARGUMENT;
+    *plain = s->last->last_plain;
+    return RG_OK;
+}
+
 rg_status rg_debug_counter_words(const rg_scene *s, int32_t first, int32_t n, uint64_t *out) {
     if (!s || !out || first < 0 || n < 0 || first + n > RG_COUNTER_WORDS) return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;

@@ -39,6 +39,7 @@ struct rg_launch_ctx {
     unsigned long long *counters = nullptr;
     int cur = 0;
     unsigned long long *last_counters = nullptr;  // the set of the latest launch (rg_debug_counters)
+    int last_plain = 0;  // the latest launch ran a PLAIN light kernel (rg_debug_last_plain)
     unsigned long long *sticky = nullptr;    // first error of any launch since rg_stream_status cleared it
     uint32_t *tile_cost = nullptr, *tile_perm = nullptr;  // probe/sort scratch (rg_launch_tile_order), order
     size_t tile_cap = 0;

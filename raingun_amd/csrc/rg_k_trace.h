@@ -12,7 +12,9 @@
 
 namespace rgk {
 
-template <bool F32F, bool BVH, class Src>
+// NODB (all three trace functions): the caller knows the scene has no disks and no boxes
+// (rg_render_kernel's PLAIN instantiations), so those sections are not compiled in.
+template <bool F32F, bool BVH, bool NODB = false, class Src>
 __device__ __forceinline__ void trace_primary(const RgKernelArgs &a, const Src &src, V3 d, Closest &c) {
     if constexpr (!BVH) sph_primary<F32F>(a, src, d, c);
     // the camera buffer's list bounds, loaded while the other bodies are tested
@@ -30,7 +32,8 @@ __device__ __forceinline__ void trace_primary(const RgKernelArgs &a, const Src &
             if (dist >= 0.0) closest_add(c, dist, rg_cptr(a.pln_id)[i]);
         }
     }
-    const V3 o = v3(0.0, 0.0, 0.0);
+    [[maybe_unused]] const V3 o = v3(0.0, 0.0, 0.0);
+    if constexpr (!NODB) {
     for (int i = 0; i < a.n_dsk; ++i) {
         RG_REGION(RGR_DISK);
         const RgDsk k = src.getd(i);
@@ -47,6 +50,7 @@ __device__ __forceinline__ void trace_primary(const RgKernelArgs &a, const Src &
             double t;
             if (aabb_hit(b, o, inv, sx, sy, sz, t)) closest_add(c, t, rg_cptr(a.box_id)[i]);
         }
+    }
     }
     if constexpr (BVH) {  // spheres last: the other bodies' hits already bound the search
         const bool ok = !c.nan && rg_bvh_ray_ok(a.bvh_obound, 0.0, 0.0, 0.0, d.x, d.y, d.z);
@@ -70,7 +74,7 @@ __device__ __forceinline__ void trace_primary(const RgKernelArgs &a, const Src &
 // !(t > light_distance)  <=>  !(min t > light_distance)  (rendering.rs:152-155),
 // so a lane stops testing at its first such hit and the wave leaves the body
 // loops as soon as every lane that is still testing is a finished shadow ray.
-template <bool F32F, bool BVH, class Src>
+template <bool F32F, bool BVH, bool NODB = false, class Src>
 __device__ __forceinline__ void trace_query(const RgKernelArgs &a, const Src &src, const Ray &r, bool shadow, double ld,
                                             Closest &c, bool &occl, bool lane_walk = false, int light = -1) {
     const V3 o = r.o, d = r.d;
@@ -103,7 +107,9 @@ __device__ __forceinline__ void trace_query(const RgKernelArgs &a, const Src &sr
             }
         }
     }
+    if constexpr (NODB && !BVH) return;  // the planes were the last bodies
     if (!__any(need)) return;
+    if constexpr (!NODB) {
     for (int i = 0; i < a.n_dsk; ++i) {
         RG_REGION(RGR_DISK);
         const RgDsk k = src.getd(i);
@@ -132,6 +138,7 @@ __device__ __forceinline__ void trace_query(const RgKernelArgs &a, const Src &sr
                 }
             }
         }
+    }
     }
     if constexpr (BVH) {  // spheres last: plane/disk/box hits already bound the search
         if (!__any(need)) return;
@@ -203,7 +210,7 @@ struct ShadowBatch {
     double ld[LB];      // light.distance(hit) (lights.rs:53-58), +inf for directional
 };
 
-template <int LB, class Src>
+template <int LB, bool NODB = false, class Src>
 __device__ __forceinline__ void trace_shadow(const RgKernelArgs &a, const Src &src, V3 o, const ShadowBatch<LB> &sb,
                                              uint32_t full, uint32_t &occl) {
     constexpr int G = RG_SHADOW_GROUP;
@@ -270,6 +277,7 @@ __device__ __forceinline__ void trace_shadow(const RgKernelArgs &a, const Src &s
             }
         }
     }
+    if constexpr (NODB) return;  // the planes were the last bodies
     if (!__any(occl != full)) return;
     for (int i = 0; i < a.n_dsk; ++i) {
         RG_REGION(RGR_DISK);

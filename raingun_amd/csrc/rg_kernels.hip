@@ -103,30 +103,32 @@ extern "C" int rg_launch_global_frames(const RgKernelArgs *a, int maxd) {
 }
 
 template <int MAXD, bool HF = false>
-static hipError_t launch_depth(const RgKernelArgs *a, hipStream_t stream, size_t *gt) {
+static hipError_t launch_depth(const RgKernelArgs *a, hipStream_t stream, size_t *gt, int *plain) {
     if (rg_heavy_path(*a)) return launch_heavy<MAXD, HF>(a, stream, gt);
     // light host frames run the MAXD == 0 kernels: array-frame HF light kernels (9 spilled
     // VGPRs) measured slower into pinned memory, 0.768 -> 0.826 ms (profiles/r06/s5)
     if constexpr (HF) return hipErrorInvalidValue;
-    else return launch_light<MAXD>(a, stream, gt);
+    else return launch_light<MAXD>(a, stream, gt, plain);
 }
 
-static hipError_t dispatch_depth(const RgKernelArgs *a, int maxd, hipStream_t stream, size_t *gt) {
+// plain (nullable): whether the launch runs a PLAIN light instantiation (rg_render_launch.h rg_light_plain)
+static hipError_t dispatch_depth(const RgKernelArgs *a, int maxd, hipStream_t stream, size_t *gt, int *plain = nullptr) {
+    if (plain) *plain = 0;
     if (a->px_mask)  // a sparse launch (rg_render_*_sparse.hip): a tile list and a pixel mask, frames in the global buffer
-        return rg_heavy_path(*a) ? launch_heavy<0, false, true>(a, stream, gt) : launch_light<0, true>(a, stream, gt);
+        return rg_heavy_path(*a) ? launch_heavy<0, false, true>(a, stream, gt) : launch_light<0, true>(a, stream, gt, plain);
     if (host_frame_launch(a)) {
         if (RG_HOST_ARRAY_FRAMES > 0 && maxd <= RG_HOST_ARRAY_FRAMES && rg_heavy_path(*a))
-            return launch_depth<8, true>(a, stream, gt);
-        return launch_depth<0>(a, stream, gt);
+            return launch_depth<8, true>(a, stream, gt, plain);
+        return launch_depth<0>(a, stream, gt, plain);
     }
-    if (maxd <= 8) return launch_depth<8>(a, stream, gt);
-    if (maxd <= 16) return launch_depth<16>(a, stream, gt);
-    if (maxd <= 64) return launch_depth<64>(a, stream, gt);
-    return launch_depth<0>(a, stream, gt);
+    if (maxd <= 8) return launch_depth<8>(a, stream, gt, plain);
+    if (maxd <= 16) return launch_depth<16>(a, stream, gt, plain);
+    if (maxd <= 64) return launch_depth<64>(a, stream, gt, plain);
+    return launch_depth<0>(a, stream, gt, plain);
 }
 
-extern "C" hipError_t rg_launch_render(const RgKernelArgs *a, int maxd, hipStream_t stream) {
-    return dispatch_depth(a, maxd, stream, nullptr);
+extern "C" hipError_t rg_launch_render(const RgKernelArgs *a, int maxd, hipStream_t stream, int *plain) {
+    return dispatch_depth(a, maxd, stream, nullptr, plain);
 }
 
 // Threads of the grid rg_launch_render would use (frame-buffer sizing for maxd > 64).

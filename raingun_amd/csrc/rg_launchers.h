@@ -6,7 +6,8 @@
 
 #include "rg_device.h"
 
-extern "C" hipError_t rg_launch_render(const RgKernelArgs *a, int maxd, hipStream_t stream);
+// plain (nullable): set to 1 when the launch runs a PLAIN light instantiation (rg_render_launch.h), else to 0
+extern "C" hipError_t rg_launch_render(const RgKernelArgs *a, int maxd, hipStream_t stream, int *plain);
 extern "C" int rg_host_array_frames(void);
 extern "C" hipError_t rg_render_grid_threads(const RgKernelArgs *a, int maxd, size_t *threads);
 extern "C" int rg_max_array_frames(void);

@@ -123,7 +123,10 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
 // tile from an atomic queue (counters[16..], sharded) and runs the per-lane
 // state machine until its 64 lanes have written their pixels.
 template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
-          bool HF = false, bool SPARSE = false>
+          bool HF = false, bool SPARSE = false, bool PLAIN = false>
+// PLAIN (LDS-blob light kernels with array frames only): the launcher has checked (rg_render_launch.h
+// rg_light_plain) that the scene has no disks and no boxes, that a.rgb, a.tile_perm and a.lbuf are null,
+// that a.nan_scene is 0 and that a.n_lights == LB, so the kernel holds them as compile-time facts.
 // SPARSE (MAXD == 0 only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
 // renders its pixel only where a.px_mask says so (adaptive anti-aliasing, rg_aa.hip; RgKernelArgs::px_mask).
 // LBT: lights per shadow batch on the light path (2, 3; -1: one light), 1: the heavy path.
@@ -142,6 +145,13 @@ void rg_render_kernel(RgKernelArgs a) {
 #endif
     constexpr bool GFRAMES = MAXD == 0;
     static_assert(!SPARSE || (MAXD == 0 && !HF), "sparse launches run the MAXD == 0 kernels");
+    static_assert(!PLAIN || (LBT != 1 && LSPH && LCOLD && MAXD != 0 && !HF && !SPARSE),
+                  "PLAIN: device-resident launches of the LDS-blob light kernels");
+    // what PLAIN fixes at compile time (the other kernels read the launch's arguments)
+    const int n_lights = PLAIN ? LB : a.n_lights;
+    const bool nan_scene = PLAIN ? false : a.nan_scene != 0;
+    float *const out_rgb = PLAIN ? nullptr : a.rgb;
+    const uint32_t *const tile_perm = PLAIN ? nullptr : a.tile_perm;
     // the launch context's other counter set (the previous launch's, read back
     // already: same stream) starts the next launch at zero -- no memset per frame
     if (blockIdx.x == 0 && a.counters_next)
@@ -183,7 +193,8 @@ void rg_render_kernel(RgKernelArgs a) {
         stage16(smem + a.lds_box, a.box, a.lds_lights - a.lds_box);
         stage16(smem + a.lds_lights, a.lights, (uint32_t)a.n_lights * (uint32_t)sizeof(RgLightDev));
         stage16(smem + a.lds_texs, a.texs, a.lds_lbuf - a.lds_texs);
-        if (a.lbuf) stage16(smem + a.lds_lbuf, a.lbuf, a.lds_bodies - a.lds_lbuf);
+        if constexpr (!PLAIN)
+            if (a.lbuf) stage16(smem + a.lds_lbuf, a.lbuf, a.lds_bodies - a.lds_lbuf);
         }
         src.f = reinterpret_cast<const RgSphF *>(smem + a.lds_sphf);
         src.f2 = reinterpret_cast<const RgSphF2 *>(smem + a.lds_sphf + (size_t)a.n_sph * sizeof(RgSphF));
@@ -421,7 +432,7 @@ void rg_render_kernel(RgKernelArgs a) {
                             occl_full = 0u;
 #pragma unroll
                             for (int l = 0; l < LB; ++l) {
-                                if (l < a.n_lights) {
+                                if (l < n_lights) {
                                     const RgLightDev L = T.lights[l];
                                     if (L.kind != RG_LIGHT_DIRECTIONAL) RG_REGION(RGR_LIGHT_SPH);
                                     light_dir_dist(L, h, sb.d[l], sb.ld[l]);
@@ -438,7 +449,7 @@ void rg_render_kernel(RgKernelArgs a) {
                                 const C3 col = texel_color(texel);
                                 park[64 * PK_COL] = col.r; park[64 * (PK_COL + 1)] = col.g; park[64 * (PK_COL + 2)] = col.b;
                             }
-                            if (a.n_lights > 0) mode = MODE_SHADOW;
+                            if (n_lights > 0) mode = MODE_SHADOW;
                             else shade = true;  // no lights: finish with black (rendering.rs:138)
                         } else {
                             bcol = surface_color(T.texs, m, b, h);
@@ -530,7 +541,7 @@ void rg_render_kernel(RgKernelArgs a) {
                 C3 acc = c3(0.0f, 0.0f, 0.0f);
 #pragma unroll
                 for (int l = 0; l < LB; ++l) {
-                    if (l < a.n_lights) {
+                    if (l < n_lights) {
                         const RgLightDev L = T.lights[l];
                         const float inten = !((occl >> l) & 1u) ? park[64 * (PK_LIN + l)] : 0.0f;
                         const float power = park[64 * (PK_PP + l)] * inten;
@@ -652,7 +663,7 @@ void rg_render_kernel(RgKernelArgs a) {
                             if (HOSTF && a.defer_px) *my_px = px;
                             else a.rgba[oidx] = px;
 #if !defined(RG_TILE_TIMES) && !defined(RG_WAVE_TIMES)
-                            if (a.rgb) { a.rgb[3 * oidx] = ret.r; a.rgb[3 * oidx + 1] = ret.g; a.rgb[3 * oidx + 2] = ret.b; }
+                            if (out_rgb) { out_rgb[3 * oidx] = ret.r; out_rgb[3 * oidx + 1] = ret.g; out_rgb[3 * oidx + 2] = ret.b; }
 #endif
                         }
                         mode = MODE_DONE;
@@ -813,7 +824,7 @@ void rg_render_kernel(RgKernelArgs a) {
                     }
                 }
                 if constexpr (SPARSE) tile = a.tile_perm[tile];  // the list entry
-                else if (a.tile_perm) tile = a.tile_perm[tile];  // scheduling order only; every tile is rendered once
+                else if (tile_perm) tile = tile_perm[tile];  // scheduling order only; every tile is rendered once
 #ifdef RG_WAVE_TIMES
                 ++wt_tiles;
 #endif
@@ -836,7 +847,7 @@ void rg_render_kernel(RgKernelArgs a) {
                     if (HOSTF && a.defer_px) *my_px = 0u;
                     else if (!HOSTF || oidx != RG_NO_PIXEL) a.rgba[oidx] = 0u;
 #if !defined(RG_TILE_TIMES) && !defined(RG_WAVE_TIMES)
-                    if (a.rgb) { a.rgb[3 * oidx] = 0.0f; a.rgb[3 * oidx + 1] = 0.0f; a.rgb[3 * oidx + 2] = 0.0f; }
+                    if (out_rgb) { out_rgb[3 * oidx] = 0.0f; out_rgb[3 * oidx + 1] = 0.0f; out_rgb[3 * oidx + 2] = 0.0f; }
 #endif
                     alive = false;
                 }
@@ -862,7 +873,7 @@ void rg_render_kernel(RgKernelArgs a) {
                     q.d = normalize(v3(sx, sy, -1.0));
                     n_prim++;
                     closest_init(c);
-                    trace_primary<F32F, BVH>(a, src, q.d, c);
+                    trace_primary<F32F, BVH, PLAIN>(a, src, q.d, c);
                     mode = MODE_CLOSEST;
                     qdepth = 0;
                     task = -1;
@@ -1026,7 +1037,7 @@ void rg_render_kernel(RgKernelArgs a) {
             // (rendering.rs:150-155; the scene.rs:38 panic iff >= 2 hits, one NaN).
             bool exact = false;
             if (mode == MODE_SHADOW) {
-                exact = a.nan_scene != 0;
+                exact = nan_scene;
 #pragma unroll
                 for (int l = 0; l < LB; ++l) exact |= ((occl_full >> l) & 1u) && ray_exotic(q.o, sb.d[l]);
             }
@@ -1046,7 +1057,7 @@ void rg_render_kernel(RgKernelArgs a) {
                         closest_init(c);
                     }
                     bool unused = false;
-                    trace_query<F32F, BVH>(a, src, rq, false, 0.0, c, unused);
+                    trace_query<F32F, BVH, PLAIN>(a, src, rq, false, 0.0, c, unused);
                     if (exact) {
                         if (c.id >= 0 && !(c.t > ld)) occl |= 1u << l;
                         if (c.nan && c.nhit >= 2) raise_error(a, pixel, RG_ERR_NAN_DISTANCE);
@@ -1056,7 +1067,7 @@ void rg_render_kernel(RgKernelArgs a) {
             if (mode == MODE_SHADOW && !exact) {
                 RG_REGION(RGR_Q_SHADOW);
                 occl = ~occl_full & ((1u << LB) - 1u);  // absent slots count as done
-                trace_shadow<LB>(a, src, q.o, sb, (1u << LB) - 1u, occl);
+                trace_shadow<LB, PLAIN>(a, src, q.o, sb, (1u << LB) - 1u, occl);
             }
         }
 #ifdef RG_TILE_TIMES

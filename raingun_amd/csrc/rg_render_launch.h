@@ -33,7 +33,7 @@ __attribute__((visibility("hidden"))) hipError_t occupancy(const void *kern, int
 // Launch (or, with grid_threads != nullptr, only size: the threads of the
 // grid, which a MAXD == 0 launch needs for its frame buffer) one instantiation.
 template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LB, bool F32F, bool BVH, bool TASKS, int TPW = 0, bool HF = false,
-          bool SPARSE = false>
+          bool SPARSE = false, bool PLAIN = false>
 static hipError_t launch_one(const RgKernelArgs *a, size_t lds, hipStream_t stream, size_t *grid_threads) {
     // Block size.  The heavy path shares one LDS copy of the scene (and the
     // BVH stacks / task pool) among the CU's 4*WPS waves: one block per CU.
@@ -43,7 +43,7 @@ static hipError_t launch_one(const RgKernelArgs *a, size_t lds, hipStream_t stre
     // waves that finished (a 4*WPS-wave block would keep the CU until its
     // slowest wave -- one refractive tile -- is done).
     constexpr int threads = LB != 1 ? 64 * RG_LIGHT_BLOCK_WAVES : 256 * WPS;  // LB != 1: the light path
-    auto kern = rg_render_kernel<MAXD, LSPH, LCOLD, WPS, LB, F32F, BVH, TASKS, TPW, HF, SPARSE>;
+    auto kern = rg_render_kernel<MAXD, LSPH, LCOLD, WPS, LB, F32F, BVH, TASKS, TPW, HF, SPARSE, PLAIN>;
     int cus = 0, per_cu = 0;
     const hipError_t oe = occupancy(reinterpret_cast<const void *>(kern), threads, lds, cus, per_cu);
     if (oe != hipSuccess) return oe;
@@ -135,12 +135,45 @@ static hipError_t launch_waves(const RgKernelArgs *a, hipStream_t stream, size_t
 #define RG_LIGHT_WPS_ONE RG_LIGHT_WPS  // the one-light batch (118 VGPRs at 4 waves per SIMD)
 #endif
 
+// Lights per shadow batch of the light kernel that a scene with n_lights lights runs (launch_light below).
+static inline int rg_light_batch(int n_lights) {
+#if RG_LB_ONE
+    if (n_lights <= 1) return 1;
+#endif
+#if RG_LB_SMALL > 1
+    if (n_lights <= RG_LB_SMALL) return RG_LB_SMALL;
+#endif
+    return RG_LB;
+}
+
+// May a device-resident light launch run the PLAIN instantiation of its kernel (rg_render_kernel.h)?  Every
+// fact that kernel holds at compile time, checked here: no disks and no boxes, no f32 RGB output, no
+// tile order, no light buffers, no NaN-scene path, a shadow batch exactly as wide as the scene's light
+// count -- and the whole scene in LDS (the PLAIN kernels are LSPH && LCOLD ones).
+static inline bool rg_light_plain(const RgKernelArgs &a) {
+    return a.n_dsk == 0 && a.n_box == 0 && a.rgb == nullptr && a.tile_perm == nullptr && a.lbuf == nullptr &&
+           a.nan_scene == 0 && a.n_lights == rg_light_batch(a.n_lights) && a.lds_total_bytes <= RG_LDS_BUDGET;
+}
+
+// One light launch: the PLAIN kernel where the launch admits it (array frames only), else launch_waves' choice.
+template <int MAXD, int WPS, int LB, int TPW>
+static hipError_t launch_light_one(const RgKernelArgs *a, hipStream_t stream, size_t *gt, bool plain) {
+    if constexpr (MAXD != 0)
+        if (plain)
+            return launch_one<MAXD, true, true, WPS, LB, false, false, false, TPW, false, false, true>(a, a->lds_total_bytes, stream, gt);
+    return launch_waves<MAXD, WPS, LB, false, false, false, TPW>(a, stream, gt);
+}
+
 // Light scenes (few bodies): per-iteration overhead dominates -> fewer,
 // fatter iterations (RG_LB shadow rays per pass) at 2 waves/SIMD.  Heavy
 // scenes: the body loop dominates and waves mix ray kinds -> one ray per
 // lane in ONE shared loop, 4 waves/SIMD to hide LDS/FP64 latency.
+// ran_plain (nullable): set to 1 when the launch runs a PLAIN instantiation, else to 0.
 template <int MAXD, bool SPARSE = false>
-__attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs *a, hipStream_t stream, size_t *gt) {
+__attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs *a, hipStream_t stream, size_t *gt,
+                                                              int *ran_plain) {
+    const bool plain = MAXD != 0 && !SPARSE && rg_light_plain(*a);
+    if (ran_plain) *ran_plain = plain ? 1 : 0;
     // a launch on its own (not one of several frames in flight): persistent waves at full
     // occupancy balance the tiles dynamically, where a fixed tiles-per-wave grid makes every
     // wave render exactly that many tiles and the slowest wave's sum the makespan
@@ -160,8 +193,8 @@ __attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs
     // one-light scenes: a batch of one (template LBT -1: 1 is the heavy path)
     if (a->n_lights <= 1) {
         if constexpr (MAXD != 0 && RG_LIGHT_SINGLE_PERSISTENT)
-            if (persistent) return launch_waves<MAXD, RG_LIGHT_WPS_ONE, -1, false, false, false, -1>(a, stream, gt);
-        return launch_waves<MAXD, RG_LIGHT_WPS_ONE, -1, false, false, false>(a, stream, gt);
+            if (persistent) return launch_light_one<MAXD, RG_LIGHT_WPS_ONE, -1, -1>(a, stream, gt, plain);
+        return launch_light_one<MAXD, RG_LIGHT_WPS_ONE, -1, 0>(a, stream, gt, plain);
     }
 #endif
 #if RG_LB_SMALL > 1
@@ -170,21 +203,21 @@ __attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs
     // at LB 2, profiles/r06/s24)
     if (a->n_lights <= RG_LB_SMALL) {
         if constexpr (MAXD != 0 && RG_LIGHT_SINGLE_PERSISTENT)
-            if (persistent) return launch_waves<MAXD, RG_LIGHT_WPS, RG_LB_SMALL, false, false, false, -1>(a, stream, gt);
-        return launch_waves<MAXD, RG_LIGHT_WPS, RG_LB_SMALL, false, false, false>(a, stream, gt);
+            if (persistent) return launch_light_one<MAXD, RG_LIGHT_WPS, RG_LB_SMALL, -1>(a, stream, gt, plain);
+        return launch_light_one<MAXD, RG_LIGHT_WPS, RG_LB_SMALL, 0>(a, stream, gt, plain);
     }
 #endif
     if constexpr (MAXD != 0 && RG_LIGHT_SINGLE_PERSISTENT)
-        if (persistent) return launch_waves<MAXD, RG_LIGHT_WPS, RG_LB, false, false, false, -1>(a, stream, gt);
+        if (persistent) return launch_light_one<MAXD, RG_LIGHT_WPS, RG_LB, -1>(a, stream, gt, plain);
 #if RG_LIGHT_TPW_BIG > 0
     // whole frames (frames in flight): RG_LIGHT_TPW_BIG tiles per wave, half the waves of
     // RG_LIGHT_TILES_PER_WAVE (as a compile-time variant: test1 0.2968 -> 0.2943 ms over 200
     // frames, profiles/r06/s43); smaller launches (the 1/N shares) keep 16
     if constexpr (MAXD != 0)
         if (rg_tile_count(*a) >= RG_LIGHT_BIG_TILES)
-            return launch_waves<MAXD, RG_LIGHT_WPS, RG_LB, false, false, false, RG_LIGHT_TPW_BIG>(a, stream, gt);
+            return launch_light_one<MAXD, RG_LIGHT_WPS, RG_LB, RG_LIGHT_TPW_BIG>(a, stream, gt, plain);
 #endif
-    return launch_waves<MAXD, RG_LIGHT_WPS, RG_LB, false, false, false>(a, stream, gt);
+    return launch_light_one<MAXD, RG_LIGHT_WPS, RG_LB, 0>(a, stream, gt, plain);
     }
 }
 
@@ -203,14 +236,14 @@ __attribute__((visibility("hidden"))) hipError_t launch_heavy(const RgKernelArgs
 }
 
 // one explicit instantiation each, in the rg_render_*.hip of that name
-extern template hipError_t launch_light<8>(const RgKernelArgs *, hipStream_t, size_t *);
-extern template hipError_t launch_light<16>(const RgKernelArgs *, hipStream_t, size_t *);
-extern template hipError_t launch_light<64>(const RgKernelArgs *, hipStream_t, size_t *);
-extern template hipError_t launch_light<0>(const RgKernelArgs *, hipStream_t, size_t *);
+extern template hipError_t launch_light<8>(const RgKernelArgs *, hipStream_t, size_t *, int *);
+extern template hipError_t launch_light<16>(const RgKernelArgs *, hipStream_t, size_t *, int *);
+extern template hipError_t launch_light<64>(const RgKernelArgs *, hipStream_t, size_t *, int *);
+extern template hipError_t launch_light<0>(const RgKernelArgs *, hipStream_t, size_t *, int *);
 extern template hipError_t launch_heavy<8, false>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_heavy<16, false>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_heavy<64, false>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_heavy<0, false>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_heavy<8, true>(const RgKernelArgs *, hipStream_t, size_t *);
-extern template hipError_t launch_light<0, true>(const RgKernelArgs *, hipStream_t, size_t *);
+extern template hipError_t launch_light<0, true>(const RgKernelArgs *, hipStream_t, size_t *, int *);
 extern template hipError_t launch_heavy<0, false, true>(const RgKernelArgs *, hipStream_t, size_t *);

@@ -2,4 +2,4 @@
 // that emits these rg_render_kernel instantiations (rg_render_launch.h).
 #include "rg_render_launch.h"
 
-template hipError_t launch_light<16>(const RgKernelArgs *, hipStream_t, size_t *);
+template hipError_t launch_light<16>(const RgKernelArgs *, hipStream_t, size_t *, int *);

@@ -3,4 +3,4 @@
 // instantiations (rg_render_launch.h).
 #include "rg_sparse_launch.h"
 
-template hipError_t launch_light<0, true>(const RgKernelArgs *, hipStream_t, size_t *);
+template hipError_t launch_light<0, true>(const RgKernelArgs *, hipStream_t, size_t *, int *);

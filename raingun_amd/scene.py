@@ -314,6 +314,12 @@ class DeviceScene:
         0 = automatic (16x4 for heavy-path scenes, 64x1 for light-path scenes)."""
         _abi.check(_abi.lib().rg_debug_set_host_tile_shape(self.handle, int(tile_wlog)))
 
+    def last_plain(self) -> bool:
+        """Did the latest render launch run a PLAIN light kernel (include/raingun_debug.h rg_debug_last_plain)?"""
+        plain = C.c_int32(-1)
+        _abi.check(_abi.lib().rg_debug_last_plain(self.handle, C.byref(plain)))
+        return plain.value == 1
+
     def bvh_info(self) -> _abi.rg_bvh_info:
         info = _abi.rg_bvh_info()
         _abi.check(_abi.lib().rg_debug_bvh_info(self.handle, C.byref(info)))

@@ -34,15 +34,18 @@ for line in remarks:
     if m and cur is not None:
         cur[m.group(1)] = int(m.group(2))
 for r in rows:
-    m = re.match(r"_Z16rg_render_kernelILi(\d+)ELb(\d)ELb(\d)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELi(n?\d+)ELb(\d)E",
-                 r["name"])
+    m = re.match(r"_Z16rg_render_kernelILi(\d+)ELb(\d)ELb(\d)ELi(\d+)ELi(n?\d+)ELb(\d)ELb(\d)ELb(\d)ELi(n?\d+)ELb(\d)E"
+                 r"(?:Lb(\d)E)?(?:Lb(\d)E)?", r["name"])
     if not m or m.group(1) != "8":
         continue
-    maxd, lsph, lcold, wps, lb, f32f, bvh, tasks, tpw, hf = m.groups()
-    kind = "light" if int(lb) > 1 else "heavy"
+    maxd, lsph, lcold, wps, lb, f32f, bvh, tasks, tpw, hf, sparse, plain = m.groups()
+    lb = lb.replace("n", "-")  # -1: the light path's one-light batch
+    kind = "light" if lb != "1" else "heavy"
     if tpw != "0":
         kind += f" tpw={tpw.replace('n', '-')}"
     if hf == "1":
         kind += " host"
-    print(f"{kind:12s} <{maxd},{lsph},{lcold},{wps},{lb},{f32f},{bvh},{tasks}>  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}"
+    if plain == "1":
+        kind += " plain"
+    print(f"{kind:18s} <{maxd},{lsph},{lcold},{wps},{lb},{f32f},{bvh},{tasks}>  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}"
           f"  scratch {r.get('ScratchSize [bytes/lane]')} B/lane  occ {r.get('Occupancy [waves/SIMD]')}  lds {r.get('LDS Size [bytes/block]')}")
