@@ -174,7 +174,7 @@ struct RgKernelArgs {
     // kernel's exact expressions -- two f64 divisions per pixel become two loads
     const double *prim_sx, *prim_sy;
     // 1: this launch is one of several frames in flight (rg_render_tiles_async):
-    // the heavy path sizes its persistent grid for throughput, not latency (launch_one)
+    // the heavy path sizes its persistent grid for throughput, not latency (rg_render_grid.h)
     uint32_t pipelined;
     // (double)width, (double)height (ray.rs:46-51 divisions): kernel arguments land in SGPRs,
     // where the kernel's own conversions would hold two loop-invariant VGPR pairs
@@ -264,6 +264,7 @@ __host__ __device__ inline unsigned long long rg_tile_count(const RgKernelArgs &
 #ifndef RG_HEAVY_WPS
 #define RG_HEAVY_WPS 3            // heavy path: waves per SIMD (block = 256 * WPS threads; 168 VGPRs)
 #endif
+#define RG_BVH_MAX_WAVES 16       // waves per block on the BVH path (256 * RG_HEAVY_WPS threads): one rg_bvh_stack row each
 #ifndef RG_HEAVY_SCENE_BODIES
 #define RG_HEAVY_SCENE_BODIES 32  // bodies per ray at which the trace loop, not shading, dominates
 #endif

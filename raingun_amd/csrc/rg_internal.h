@@ -74,7 +74,7 @@ struct rg_launch_ctx {
 #endif
 #ifndef RG_HOST_TILE_WLOG_LIGHT
 // one-launch host-visible frames of light-path scenes: 64x1 tiles, so that a wave's ring of
-// consecutive tiles (rg_render_kernel.h RG_HOST_RING) is one contiguous run of host memory
+// consecutive tiles (rg_render_cfg.h RG_HOST_RING) is one contiguous run of host memory
 #define RG_HOST_TILE_WLOG_LIGHT 6
 #endif
 #ifndef RG_HOST_TILE_WLOG

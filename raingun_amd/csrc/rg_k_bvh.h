@@ -28,7 +28,6 @@ namespace rgk {
 // already saw a NaN distance (AABB; nhit must stay exact) use the brute-force
 // loop instead.
 #define RG_BVH_STACK 64
-#define RG_BVH_MAX_WAVES 16   // waves per block on the BVH path (256 * RG_HEAVY_WPS threads)
 __shared__ int rg_bvh_stack[RG_BVH_MAX_WAVES][RG_BVH_STACK];  // allocated only by kernels that traverse
 
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }

@@ -54,6 +54,14 @@ __device__ __forceinline__ int32_t f32_to_i32(float v) {
     return (int32_t)v;
 }
 
+// Lane l's value of a double (two 32-bit readlanes).
+__device__ __forceinline__ double readlane_d(double v, int l) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // Region visit counts (diagnostic build -DRG_REGION_STATS; scripts/region_stats.py): every time a
 // wave enters region k, its first active lane adds 1 to counters[RG_REGION_BASE + 2k] and the
 // active lanes to [+ 2k + 1] -- the dynamic weights of the static ISA budget (scripts/isa_budget.py).

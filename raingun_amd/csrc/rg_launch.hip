@@ -374,7 +374,7 @@ rg_status rg_render_tiles_async(const rg_scene *s, uint32_t width, uint32_t heig
 rg_status rg_render_tiles_pipelined(const rg_scene *s, uint32_t width, uint32_t height, const rg_tiling *tiling,
                                     uint8_t *rgba_dev, float *rgb_dev, void *stream) {
     // one of several frames in flight (rg_frames, bench.py): the heavy path sizes
-    // its grid for throughput (rg_render_launch.h launch_one, RgKernelArgs::pipelined)
+    // its grid for throughput (rg_render_grid.h, RgKernelArgs::pipelined)
     rg_launch_desc d = device_frame(width, height, tiling, rgba_dev, rgb_dev, static_cast<hipStream_t>(stream));
     d.pipelined = true;
     return rg_launch_tiles(s, d);

@@ -18,81 +18,30 @@
 // Division and sqrt are the correctly-rounded hipcc expansions.
 //
 // The device code it is built from, one concern per header: rg_k_math.h, rg_k_intersect.h,
-// rg_k_bvh.h, rg_k_trace.h, rg_k_shade.h, rg_k_frames.h, rg_k_pool.h.  Launch policy:
-// rg_render_launch.h, instantiated per frame-stack depth and path by rg_render_*.hip.
+// rg_k_bvh.h, rg_k_trace.h, rg_k_shade.h, rg_k_frames.h, rg_k_pool.h; the RG_ITER_STATS
+// counters: rg_k_diag.h.  What the template parameters mean, with every constant derived from
+// them: rg_render_cfg.h.  Launch policy: rg_render_launch.h (grid: rg_render_grid.h), instantiated
+// per frame-stack depth and path by rg_render_*.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/raingun.h"
 #include "rg_device.h"
 #include "rg_k_bvh.h"
+#include "rg_k_diag.h"
 #include "rg_k_frames.h"
 #include "rg_k_intersect.h"
 #include "rg_k_math.h"
 #include "rg_k_pool.h"
 #include "rg_k_shade.h"
 #include "rg_k_trace.h"
+#include "rg_render_cfg.h"
 
 #pragma clang fp contract(off)
 
-namespace rgk {
-
-// ---------------------------------------------------------------- scheduling tunables
-#ifndef RG_PIPE_TILES_PER_WAVE
-#define RG_PIPE_TILES_PER_WAVE 64  // heavy launches with frames in flight (launch_one, RgKernelArgs::pipelined;
-                                   // 32 -> 64: configs[4] scene at 1080p 2.50 -> 2.33 ms, profiles/r05/s21)
-#endif
-#ifndef RG_PIPE_MIN_CU_DIV
-#define RG_PIPE_MIN_CU_DIV 4  // ... and at least 1/this of the CUs' blocks (3 -> 4: north-star 1/8 share 0.349 -> 0.327 ms)
-#endif
-// Light path, non-persistent waves: a wave renders at most this many 8x8 tiles
-// and exits, and the grid holds one wave per that many tiles, so the hardware
-// dispatcher hands out CU slots wave by wave -- across the kernels of frames in
-// flight too -- instead of 3072 persistent waves pinning their slots until the
-// frame's queue is empty.  16 measured best for the whole 4K frame and for
-// 1/2 .. 1/8 shares (profiles/r01/variants_light_tiles_per_wave.txt; 12 / 20 / 32
-// re-measured in rounds 3-4: profiles/r04/s29, profiles/r04/s13).
-#ifndef RG_LIGHT_TILES_PER_WAVE
-#define RG_LIGHT_TILES_PER_WAVE 16
-#endif
-#ifndef RG_HEAVY_TILES_PER_WAVE
-#define RG_HEAVY_TILES_PER_WAVE 0  // heavy path: 0 = persistent blocks (one per CU)
-#endif
-#ifndef RG_SHADOW_FAN
-// heavy path, single small launches (TASKS): up to this many more lights of a hit traced by idle
-// lanes per iteration.  Off for frames in flight and whole frames since the light buffers made
-// shadow rays cheap: north star 1.594 -> 1.497 ms (8K 5.38 -> 5.06), while a 1/8 share as one
-// launch keeps it (slowest share 0.648 vs 0.712 ms without; profiles/r05/s20, s21)
-#define RG_SHADOW_FAN 3
-#endif
-__device__ __forceinline__ double readlane_d(double v, int l) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-#ifndef RG_HEAVY_TASKS
-#define RG_HEAVY_TASKS 1   // task splitting on the heavy path, for launches of fewer than RG_HEAVY_TASK_TILES tiles
-#endif
-#ifndef RG_HEAVY_TASK_TILES
-// Task splitting shortens the slowest pixels' ray trees, which bound a small
-// launch; on a large one (and with frames in flight, whose next frame fills
-// the tail) its bookkeeping costs more than it saves: with 4 frames in flight
-// synth1024 4K 3.10 -> 2.88 ms and 8K 11.18 -> 9.94 ms without it, but a 1/8
-// share (16k tiles) 0.538 -> 0.561 ms (profiles/r01/variants_heavy_tasks.txt)
-#define RG_HEAVY_TASK_TILES 24576
-#endif
-
-}  // namespace rgk
-
 using namespace rgk;
 
-#ifndef RG_HOST_RING
-#define RG_HOST_RING 16  // light path into pinned host memory: tiles per queue group and ring flush (0: one store per tile)
-#endif
-#ifndef RG_LIGHT_BLOCK_WAVES
-#define RG_LIGHT_BLOCK_WAVES 1  // light path: waves per block (blocks retire wave by wave)
-#endif
+// (the scheduling tunables the kernel's configuration is derived from: rg_render_cfg.h)
 #ifndef RG_NQ
 #define RG_NQ 8   // tile-queue heads (see the kernel's tile loop)
 #endif
@@ -116,37 +65,28 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
 
 // Render kernel.  Heavy path: ONE persistent block of 256*WPS threads per CU
 // (WPS waves per SIMD).  Light path: one-wave blocks, each rendering at most
-// RG_LIGHT_TILES_PER_WAVE tiles (launcher: launch_one).  A block stages the
+// RG_LIGHT_TILES_PER_WAVE tiles (grid: rg_render_grid.h).  A block stages the
 // scene into LDS (LSPH: sphere, plane, disk and box tables, lights, texture
 // descriptors; LCOLD: bodies, materials; LCOLD without LSPH: only the BVH nodes, after the per-lane
 // walk stacks -- scenes whose sphere tables exceed the budget), then every wave repeatedly takes the next 8x8 pixel
 // tile from an atomic queue (counters[16..], sharded) and runs the per-lane
 // state machine until its 64 lanes have written their pixels.
-template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
-          bool HF = false, bool SPARSE = false, bool PLAIN = false>
+// What the twelve parameters mean, and every fact derived from them (K:: below): rg_render_cfg.h.
 // PLAIN (LDS-blob light kernels with array frames only): the launcher has checked (rg_render_launch.h
 // rg_light_plain) that the scene has no disks and no boxes, that a.rgb, a.tile_perm and a.lbuf are null,
 // that a.nan_scene is 0 and that a.n_lights == LB, so the kernel holds them as compile-time facts.
 // SPARSE (MAXD == 0 only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
 // renders its pixel only where a.px_mask says so (adaptive anti-aliasing, rg_aa.hip; RgKernelArgs::px_mask).
-// LBT: lights per shadow batch on the light path (2, 3; -1: one light), 1: the heavy path.
-// HF: the host-frame features (HOSTF below) with MAXD array frames.  TPW: light path, tiles per wave (0: RG_LIGHT_TILES_PER_WAVE; < 0: persistent waves that take tiles
-// until the queue is empty -- single launches, whose makespan is their slowest wave's tile sum).  Light path (LBT != 1): blocks of RG_LIGHT_BLOCK_WAVES waves, at least WPS waves
-// per SIMD (the second bound is waves per execution unit on AMD); heavy path:
-// one block of 4*WPS waves per CU.  Both cap the VGPRs at 512 / WPS.
-__global__ __launch_bounds__(LBT != 1 ? 64 * RG_LIGHT_BLOCK_WAVES : 256 * WPS, LBT != 1 ? WPS : 1)
+template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
+          bool HF = false, bool SPARSE = false, bool PLAIN = false>
+__global__ __launch_bounds__(64 * rg_block_waves(LBT, WPS), rg_min_waves_per_eu(LBT, WPS))
 void rg_render_kernel(RgKernelArgs a) {
-    constexpr int LB = LBT < 0 ? -LBT : LBT;  // lights per shadow batch (1 on the heavy path)
-    constexpr bool LIGHTP = LBT != 1;         // the light path
-    static_assert(!BVH || 4 * WPS <= RG_BVH_MAX_WAVES, "one BVH stack per wave");
+    using K = RenderCfg<MAXD, LSPH, LCOLD, WPS, LBT, F32F, BVH, TASKS, TPW, HF, SPARSE, PLAIN>;
+    constexpr int LB = K::lights_per_batch;  // shorthand: the per-light loops below are unrolled over it
 #ifdef RG_WAVE_TIMES  // diagnostic: per-wave start (before staging), staged, end (100 MHz ticks), tiles
     const unsigned long long t_wave0 = wall_clock64();
     uint32_t wt_tiles = 0;
 #endif
-    constexpr bool GFRAMES = MAXD == 0;
-    static_assert(!SPARSE || (MAXD == 0 && !HF), "sparse launches run the MAXD == 0 kernels");
-    static_assert(!PLAIN || (LBT != 1 && LSPH && LCOLD && MAXD != 0 && !HF && !SPARSE),
-                  "PLAIN: device-resident launches of the LDS-blob light kernels");
     // what PLAIN fixes at compile time (the other kernels read the launch's arguments)
     const int n_lights = PLAIN ? LB : a.n_lights;
     const bool nan_scene = PLAIN ? false : a.nan_scene != 0;
@@ -157,12 +97,11 @@ void rg_render_kernel(RgKernelArgs a) {
     if (blockIdx.x == 0 && a.counters_next)
         for (uint32_t k = threadIdx.x; k < RG_COUNTER_WORDS; k += blockDim.x) a.counters_next[k] = 0ull;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool LNODES = !LSPH && LCOLD && BVH;  // only the BVH nodes in LDS (SphNodesLds)
-    typename std::conditional<LSPH, SphLds, typename std::conditional<LNODES, SphNodesLds, SphScalar>::type>::type src;
+    typename std::conditional<LSPH, SphLds, typename std::conditional<K::lds_nodes_only, SphNodesLds, SphScalar>::type>::type src;
     Cold T;
     // light path: every one-wave block stages its own copy of the (few-KB) scene; with the
     // arena's device image that is one loop with all its loads in flight at once
-    const bool blob = LIGHTP && LSPH && LCOLD && a.lds_blob != nullptr;
+    const bool blob = K::light && LSPH && LCOLD && a.lds_blob != nullptr;
     if (blob) {
         const uint4 *g = reinterpret_cast<const uint4 *>(a.lds_blob);
         uint4 *d = reinterpret_cast<uint4 *>(smem);
@@ -214,7 +153,7 @@ void rg_render_kernel(RgKernelArgs a) {
         src.pl = rg_cptr(a.pln);
         src.dk = rg_cptr(a.dsk);
         src.bx = rg_cptr(a.box);
-        if constexpr (LNODES) {  // the nodes after the per-lane walk stacks
+        if constexpr (K::lds_nodes_only) {  // the nodes after the per-lane walk stacks
             stage16(smem + a.lds_lstack_bytes, a.nodes, (uint32_t)a.n_nodes * (uint32_t)sizeof(RgBvhNode));
             src.nd = reinterpret_cast<const RgBvhNode *>(smem + a.lds_lstack_bytes);
         } else {
@@ -252,21 +191,16 @@ void rg_render_kernel(RgKernelArgs a) {
     // store per tile (flush_tile): every store is a PCIe write whose
     // acknowledgement the wave's next vmcnt wait would otherwise sit out once
     // per finishing lane.
-    // Host-frame features (deferred tile stores, tile publication, streaming
-    // cancellation, tile shapes other than 8x8) exist only in the MAXD == 0
-    // instantiations, which host-visible one-launch renders use: the array
-    // instantiations of device-resident renders stay as lean as before (the
-    // runtime checks alone cost test1 3 %, profiles/r02/ab_hostf.txt).
-    constexpr bool HOSTF = MAXD == 0 || HF;
-    __shared__ uint32_t tile_px[HOSTF ? (LIGHTP ? RG_LIGHT_BLOCK_WAVES : 4 * WPS) : 1][64];
-    uint32_t *my_px = &tile_px[HOSTF ? threadIdx.x >> 6 : 0][lane];
+    // (a host-frame feature, K::host_frames: the array kernels of device-resident renders go without)
+    __shared__ uint32_t tile_px[K::tile_px_rows][64];
+    uint32_t *my_px = &tile_px[K::host_frames ? threadIdx.x >> 6 : 0][lane];
     // Light path into page-locked host memory without tile publication: the
     // finished tiles of a wave collect in an LDS ring and go out RING at a time.
     // A store to host memory completes only after its PCIe round trip, and on
     // gfx9 every later `s_waitcnt vmcnt` (a texel load, a frame pop from the
     // global frame buffer) waits for it too: one flush per RING tiles instead of
     // one per tile.
-    constexpr int RING = (HOSTF && LIGHTP) ? RG_HOST_RING : 0;
+    constexpr int RING = K::ring;
     __shared__ uint32_t ring_px[RING > 0 ? RG_LIGHT_BLOCK_WAVES : 1][RING > 0 ? RING : 1][64];
     __shared__ uint32_t ring_tile[RING > 0 ? RG_LIGHT_BLOCK_WAVES : 1][RING > 0 ? RING : 1];
     [[maybe_unused]] const uint32_t rw = RING > 0 ? (threadIdx.x >> 6) % RG_LIGHT_BLOCK_WAVES : 0u;
@@ -277,8 +211,8 @@ void rg_render_kernel(RgKernelArgs a) {
     // that only the query's own state is held in VGPRs across the trace.
     constexpr int PK_PP = 0, PK_LIN = LB, PK_REFL = 2 * LB, PK_COL = 2 * LB + 1, PK_KIND = 2 * LB + 4,
                   PK_R = 2 * LB + 5, PK_N = 2 * LB + 6;
-    __shared__ float park_lds[LIGHTP ? RG_LIGHT_BLOCK_WAVES : 1][LIGHTP ? PK_N : 1][64];
-    float *park = &park_lds[LIGHTP ? (threadIdx.x >> 6) % RG_LIGHT_BLOCK_WAVES : 0][0][lane];  // field k at park[64 k]
+    __shared__ float park_lds[K::light ? RG_LIGHT_BLOCK_WAVES : 1][K::light ? PK_N : 1][64];
+    float *park = &park_lds[K::light ? (threadIdx.x >> 6) % RG_LIGHT_BLOCK_WAVES : 0][0][lane];  // field k at park[64 k]
 #ifdef RG_BVH_STATS
     if (lane < 16) rg_stat_lds[(threadIdx.x >> 6) % RG_BVH_MAX_WAVES][lane] = 0ull;
 #endif
@@ -286,7 +220,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #ifdef RG_WAVE_TIMES
     const unsigned long long t_staged = wall_clock64();
 #endif
-    const uint32_t twlog = HOSTF ? a.tile_wlog : 3u, twmask = (1u << twlog) - 1u, th = 64u >> twlog;
+    const uint32_t twlog = K::host_frames ? a.tile_wlog : 3u, twmask = (1u << twlog) - 1u, th = 64u >> twlog;
     const uint32_t tiles_x = (a.width + twmask) >> twlog;
     const uint32_t ntiles = tiles_x * ((a.out_rows + th - 1u) / th);
     const C3 def = c3(a.def[0], a.def[1], a.def[2]);
@@ -316,7 +250,7 @@ void rg_render_kernel(RgKernelArgs a) {
         nring = 0;
     };
     uint32_t n_prim = 0, n_shadow = 0, n_sec = 0;
-    FrameStack<GFRAMES ? 0 : MAXD> stk;  // GFRAMES: field-major frames in a global buffer, no scratch array
+    FrameStack<MAXD> stk;  // K::global_frames (MAXD 0): field-major frames in a global buffer, no scratch array
     stk.init(a);
 
     // Sharded tile queue: RG_NQ heads, head q serving tiles q, q + RG_NQ, ... (one
@@ -361,7 +295,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #endif
     for (;;) {
         RG_REGION(RGR_LOOP);
-        if constexpr (!LIGHTP && TASKS && RG_SHADOW_FAN > 0) {
+        if constexpr (K::shadow_fan) {
             // shadow fan-out, collect: the helpers' occlusion bits (every lane active here)
             if (__any(nfan > 0)) {
                 fan_bits = 0u;
@@ -397,7 +331,7 @@ void rg_render_kernel(RgKernelArgs a) {
                     V3 n;
                     if (!surface_normal(b, h, n)) raise_error(a, pixel, RG_ERR_AABB_NORMAL);
                     if (m.surface != RG_SURFACE_REFRACTIVE) {
-                        if constexpr (LIGHTP) {
+                        if constexpr (K::light) {
                             // ONE batch covers every light (n_lights <= LB on this path): set it
                             // up now, with the per-light shading factors (parked in LDS), so that
                             // no hit-point state (h, n, incident) has to survive the shadow pass
@@ -532,7 +466,7 @@ void rg_render_kernel(RgKernelArgs a) {
             } else if (rmode == MODE_SHADOW) {
                 shade = true;  // a shadow result for light li
             }
-            if constexpr (LIGHTP) {
+            if constexpr (K::light) {
               if (shade) {
                 RG_REGION(RGR_SHADE);
                 // shade_diffuse accumulation over the batch (rendering.rs:141-170), in light order
@@ -588,7 +522,7 @@ void rg_render_kernel(RgKernelArgs a) {
                             fin = cadd(fin, cmul(bcol, lc));
                         }
                     }
-                    if constexpr (!LIGHTP && TASKS && RG_SHADOW_FAN > 0) {
+                    if constexpr (K::shadow_fan) {
                         // the lights helper lanes traced, in light order (rendering.rs:141-170)
                         for (int k = 0; k < nfan; ++k) {
                             const RgLightDev L = T.lights[li + 1 + k];
@@ -660,11 +594,9 @@ void rg_render_kernel(RgKernelArgs a) {
                         if (!handed) {
                             const uint32_t px = f32_to_u8(ret.r * 255.0f) | (f32_to_u8(ret.g * 255.0f) << 8) |
                                                 (f32_to_u8(ret.b * 255.0f) << 16) | 0xFF000000u;
-                            if (HOSTF && a.defer_px) *my_px = px;
+                            if (K::host_frames && a.defer_px) *my_px = px;
                             else a.rgba[oidx] = px;
-#if !defined(RG_TILE_TIMES) && !defined(RG_WAVE_TIMES)
-                            if (out_rgb) { out_rgb[3 * oidx] = ret.r; out_rgb[3 * oidx + 1] = ret.g; out_rgb[3 * oidx + 2] = ret.b; }
-#endif
+                            if (KDiag::rgb_is_output && out_rgb) { out_rgb[3 * oidx] = ret.r; out_rgb[3 * oidx + 1] = ret.g; out_rgb[3 * oidx + 2] = ret.b; }
                         }
                         mode = MODE_DONE;
                         break;
@@ -726,7 +658,7 @@ void rg_render_kernel(RgKernelArgs a) {
         }
         have_result = false;
         // every lane of the wave is done: its tile is complete (owners hold their pixels)
-        if (HOSTF && my_tile != 0xFFFFFFFFu && (a.defer_px || a.tile_flags) && !__any(mode != MODE_DONE)) {
+        if (K::host_frames && my_tile != 0xFFFFFFFFu && (a.defer_px || a.tile_flags) && !__any(mode != MODE_DONE)) {
             bool ringed = false;
             if constexpr (RING > 0) {
                 if (use_ring) {
@@ -755,7 +687,7 @@ void rg_render_kernel(RgKernelArgs a) {
             if constexpr (RING > 0) {  // the rest of the wave's group of consecutive tiles
                 if (use_ring && grp_next < grp_end) tile = grp_next++;
             }
-            if (HOSTF && a.cancel) {  // streaming: the consumer stopped (rendering.rs:53-67 `.all` short-circuits)
+            if (K::host_frames && a.cancel) {  // streaming: the consumer stopped (rendering.rs:53-67 `.all` short-circuits)
                 uint32_t cv = 0u;
                 if (lane == 0) cv = __hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 if (__builtin_amdgcn_readfirstlane(__shfl((int)cv, 0, 64)) != 0) qtried = RG_NQ;
@@ -768,10 +700,10 @@ void rg_render_kernel(RgKernelArgs a) {
             // box, interleaved: test1 0.2972 -> 0.2939 ms over 200 frames, test3 0.2656 -> 0.2631:
             // profiles/r04/s21/session.txt, s22).  Not on the heavy path: a claimed tile waits
             // behind the wave's current (long) one, which lengthens the tail (north star +0.6 %);
-            // nor in the light path's persistent single launches (TPW < 0), for the same reason:
+            // nor in the light path's persistent single launches (persistent waves), for the same reason:
             // rg_render_multi's shares, whose waves ended by 84 us (p50) while claimed tiles still
             // started at 145 us (profiles/r05/s18, s26)
-            if constexpr (!HOSTF && LIGHTP && TPW >= 0) {
+            if constexpr (K::slot_prefetch) {
                 if (pf_valid) {  // the slot claimed at the previous tile's start
                     const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)pf_k, 0, 64));
                     const unsigned long long t = (unsigned long long)k * RG_NQ + qi;
@@ -805,15 +737,12 @@ void rg_render_kernel(RgKernelArgs a) {
             if (tile == 0xFFFFFFFFu) {
                 tiles_left = false;
             } else {
-                constexpr uint32_t kmax = MAXD == 0 || HF || TPW < 0 ? 0u
-                                          : LIGHTP ? (TPW > 0 ? (uint32_t)TPW : RG_LIGHT_TILES_PER_WAVE)
-                                                   : RG_HEAVY_TILES_PER_WAVE;
-                if constexpr (kmax > 0) {
-                    // non-persistent: a wave renders at most kmax tiles, so the grid
+                if constexpr (!K::persistent) {
+                    // a wave renders at most that many tiles, so the grid
                     // drains through the hardware dispatcher wave (block) by wave
-                    if (++tiles_taken >= kmax) tiles_left = false;
+                    if (++tiles_taken >= K::tiles_per_wave) tiles_left = false;
                 }
-                if constexpr (!HOSTF && LIGHTP && TPW >= 0) {
+                if constexpr (K::slot_prefetch) {
                     // claim the wave's NEXT queue slot now: the atomic's round trip overlaps this
                     // tile's work instead of stalling the wave between tiles (the wave renders
                     // the claimed tile, or finds the head drained, at its next tile start)
@@ -828,7 +757,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #ifdef RG_WAVE_TIMES
                 ++wt_tiles;
 #endif
-                if constexpr (HOSTF) my_tile = tile;
+                if constexpr (K::host_frames) my_tile = tile;
                 const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
 #ifdef RG_TILE_TIMES
                 cur_tile = tile;
@@ -840,15 +769,13 @@ void rg_render_kernel(RgKernelArgs a) {
                 const uint32_t orow = ty * th + ((uint32_t)lane >> twlog);
                 bool alive = x < a.width && orow < a.out_rows;
                 const uint32_t y = alive ? out_row_to_y(a, orow) : 0u;
-                oidx = (HOSTF && !alive) ? RG_NO_PIXEL : (size_t)out_row_of(a, orow) * a.width + x;
-                if (HOSTF && a.image_rows && alive)  // the whole image: the pixel's own row (padding: no store)
+                oidx = (K::host_frames && !alive) ? RG_NO_PIXEL : (size_t)out_row_of(a, orow) * a.width + x;
+                if (K::host_frames && a.image_rows && alive)  // the whole image: the pixel's own row (padding: no store)
                     oidx = y == 0xFFFFFFFFu ? RG_NO_PIXEL : (size_t)y * a.width + x;
                 if (alive && y == 0xFFFFFFFFu) {  // padding row of a partial last tile
-                    if (HOSTF && a.defer_px) *my_px = 0u;
-                    else if (!HOSTF || oidx != RG_NO_PIXEL) a.rgba[oidx] = 0u;
-#if !defined(RG_TILE_TIMES) && !defined(RG_WAVE_TIMES)
-                    if (out_rgb) { out_rgb[3 * oidx] = 0.0f; out_rgb[3 * oidx + 1] = 0.0f; out_rgb[3 * oidx + 2] = 0.0f; }
-#endif
+                    if (K::host_frames && a.defer_px) *my_px = 0u;
+                    else if (!K::host_frames || oidx != RG_NO_PIXEL) a.rgba[oidx] = 0u;
+                    if (KDiag::rgb_is_output && out_rgb) { out_rgb[3 * oidx] = 0.0f; out_rgb[3 * oidx + 1] = 0.0f; out_rgb[3 * oidx + 2] = 0.0f; }
                     alive = false;
                 }
                 if constexpr (SPARSE) {  // once per tile: only the samples of flagged pixels are traced
@@ -862,7 +789,7 @@ void rg_render_kernel(RgKernelArgs a) {
                     // heavy path: the host's per-column / per-row table of the same expressions
                     // (north star -1 %); the light path keeps the divisions (the loads at the
                     // tile's start cost it more than they save: test1 +0.5 %, test3 +1.5 %)
-                    if (!LIGHTP && a.prim_sx) {
+                    if (!K::light && a.prim_sx) {
                         sx = a.prim_sx[x];
                         sy = a.prim_sy[y];
                     } else {
@@ -882,7 +809,7 @@ void rg_render_kernel(RgKernelArgs a) {
                 continue;
             }
         }
-        if constexpr (!LIGHTP && TASKS && RG_SHADOW_FAN > 0) {
+        if constexpr (K::shadow_fan) {
             // shadow fan-out, assign: a lane about to trace the shadow ray of light li
             // hands lights li+1.. of the same hit to idle lanes of its wave, so up to
             // 1 + RG_SHADOW_FAN shadow rays of a hit are traced in one iteration instead
@@ -969,36 +896,7 @@ void rg_render_kernel(RgKernelArgs a) {
             have_result = mode == MODE_WAIT;
             continue;
         }
-#ifdef RG_ITER_STATS
-        {  // SIMD use of the query iterations (diagnostic build), counters[4..11]: query
-           // iterations, their querying lanes; iterations with a ray of depth >= 1, their
-           // querying lanes, their depth >= 1 lanes; iterations with <= 16 querying lanes;
-           // iterations with shadow lanes, shadow lanes
-            const int qd = mode == MODE_CLOSEST ? qdepth : hdepth;
-            const unsigned long long all = __ballot(querying), sec = __ballot(querying && qd >= 1);
-            const unsigned long long shl = __ballot(querying && mode != MODE_CLOSEST);
-            const unsigned n = (unsigned)__builtin_popcountll(all);
-            if (lane == __builtin_ffsll((long long)__ballot(1)) - 1) {  // one atomic set per wave iteration
-                atomicAdd(&a.counters[4], 1ull);
-                atomicAdd(&a.counters[5], (unsigned long long)n);
-                if (sec) {
-                    atomicAdd(&a.counters[6], 1ull);
-                    atomicAdd(&a.counters[7], (unsigned long long)n);
-                    atomicAdd(&a.counters[8], (unsigned long long)__builtin_popcountll(sec));
-                }
-                if (n <= 16) atomicAdd(&a.counters[9], 1ull);
-                if (shl) {
-                    atomicAdd(&a.counters[10], 1ull);
-                    atomicAdd(&a.counters[11], (unsigned long long)__builtin_popcountll(shl));
-                }
-                // light path (no BVH walk words): iterations with closest-hit lanes, those lanes
-                if (LIGHTP && (all & ~shl)) {
-                    atomicAdd(&a.counters[14], 1ull);
-                    atomicAdd(&a.counters[15], (unsigned long long)__builtin_popcountll(all & ~shl));
-                }
-            }
-        }
-#endif
+        KDiag::iter_stats<K::light>(a, lane, querying, mode, mode == MODE_CLOSEST ? qdepth : hdepth);
 #ifdef RG_TILE_TIMES
         ++tile_iters;
         const unsigned long long t_q0 = wall_clock64();
@@ -1007,7 +905,7 @@ void rg_render_kernel(RgKernelArgs a) {
             closest_init(c);
             occl = 0u;
         }
-        if constexpr (!LIGHTP) {
+        if constexpr (!K::light) {
             // one ray per lane, one pass: closest-hit and shadow lanes share the
             // body loop (best when a wave mixes ray kinds over many bodies)
             if (querying) {
@@ -1075,7 +973,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #endif
         have_result = querying || mode == MODE_WAIT;
     }
-    if (HOSTF && my_tile != 0xFFFFFFFFu && (a.defer_px || a.tile_flags)) {
+    if (K::host_frames && my_tile != 0xFFFFFFFFu && (a.defer_px || a.tile_flags)) {
         bool ringed = false;
         if constexpr (RING > 0) {
             if (use_ring) {
@@ -1091,7 +989,7 @@ void rg_render_kernel(RgKernelArgs a) {
         if (use_ring) flush_ring();
     }
 #ifdef RG_TILE_TIMES
-    if (cur_tile != 0xFFFFFFFFu && lane == 0 && a.rgb) {
+    if (cur_tile != 0xFFFFFFFFu && lane == 0 && a.rgb) {  // the wave's last tile: as at a tile's start above
         a.rgb[cur_tile] = (float)(wall_clock64() - t_tile) * 0.01f;
         a.rgb[ntiles + cur_tile] = (float)tile_iters;
         a.rgb[2 * ntiles + cur_tile] = (float)(t_tile & 0xFFFFFFull);

@@ -35,10 +35,12 @@ import subprocess
 import sys
 from pathlib import Path
 
+from render_kernel_name import HEADLINE, parse
+
 CSRC = Path(__file__).resolve().parent.parent / "raingun_amd" / "csrc"
 # the headers that hold the kernel's device code: instructions are attributed by (file, line)
 SRCS = {p.name: p for p in sorted(CSRC.glob("rg_k_*.h")) + [CSRC / "rg_render_kernel.h"]}
-DEFAULT = "_Z16rg_render_kernelILi8ELb1ELb1ELi4ELi3ELb0ELb0ELb0ELi0ELb0EEv12RgKernelArgs"
+DEFAULT = HEADLINE  # the PLAIN light kernel of the headline benchmark (--heavy: give a --kernel of that file)
 LLVM = "/opt/rocm/lib/llvm/bin"
 # callers of sphere_tail -> the pair region its inlined instructions belong to
 PAIR_OF = {"sph_primary_group": "RGR_PRIM_PAIR", "sph_query_group": "RGR_QC_PAIR", "trace_shadow": "RGR_SH_PAIR"}
@@ -185,6 +187,8 @@ def main():
             del args[k:k + 2]
             kernel, out_json, visits_path = ((v, out_json, visits_path) if flag == "--kernel" else
                                              (kernel, v, visits_path) if flag == "--json" else (kernel, out_json, v))
+    if parse(kernel) is None:
+        sys.exit(f"not the mangled name of an rg_render_kernel instantiation: {kernel}")
     unit = "rg_render_light_d8"
     if "--heavy" in args:  # the heavy-path instantiations (give their --kernel)
         args.remove("--heavy")

@@ -11,6 +11,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+from render_kernel_name import describe, parse
+
 CSRC = Path(__file__).resolve().parent.parent / "raingun_amd" / "csrc"
 UNITS = ["rg_render_heavy_d8_host", "rg_render_light_d8", "rg_render_heavy_d8"]
 procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
@@ -34,18 +36,9 @@ for line in remarks:
     if m and cur is not None:
         cur[m.group(1)] = int(m.group(2))
 for r in rows:
-    m = re.match(r"_Z16rg_render_kernelILi(\d+)ELb(\d)ELb(\d)ELi(\d+)ELi(n?\d+)ELb(\d)ELb(\d)ELb(\d)ELi(n?\d+)ELb(\d)E"
-                 r"(?:Lb(\d)E)?(?:Lb(\d)E)?", r["name"])
-    if not m or m.group(1) != "8":
+    k = parse(r["name"])
+    if k is None or k["MAXD"] != 8:
         continue
-    maxd, lsph, lcold, wps, lb, f32f, bvh, tasks, tpw, hf, sparse, plain = m.groups()
-    lb = lb.replace("n", "-")  # -1: the light path's one-light batch
-    kind = "light" if lb != "1" else "heavy"
-    if tpw != "0":
-        kind += f" tpw={tpw.replace('n', '-')}"
-    if hf == "1":
-        kind += " host"
-    if plain == "1":
-        kind += " plain"
-    print(f"{kind:18s} <{maxd},{lsph},{lcold},{wps},{lb},{f32f},{bvh},{tasks}>  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}"
+    args = ",".join(str(int(k[n])) for n in ("MAXD", "LSPH", "LCOLD", "WPS", "LBT", "F32F", "BVH", "TASKS"))
+    print(f"{describe(k):18s} <{args}>  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}"
           f"  scratch {r.get('ScratchSize [bytes/lane]')} B/lane  occ {r.get('Occupancy [waves/SIMD]')}  lds {r.get('LDS Size [bytes/block]')}")

@@ -15,8 +15,10 @@ import pytest
 
 CSRC = Path(__file__).resolve().parent.parent / "raingun_amd" / "csrc"
 HIPCC = "/opt/rocm/bin/hipcc"
-# every translation unit that includes a kernel header: the nine rg_render_*.hip (one group of
-# rg_render_kernel instantiations each), the launchers with rg_trace_kernel, the tile-order kernels
+# every translation unit that includes a kernel header directly: nine of the eleven rg_render_*.hip
+# (one group of rg_render_kernel instantiations each; the two sparse ones take theirs through
+# rg_sparse_launch.h and are compiled by tests/test_aa_adaptive_cpu.py), the launchers with
+# rg_trace_kernel, the tile-order kernels: eleven units
 KERNEL_UNITS = sorted(p.name for p in CSRC.glob("*.hip")
                       if any(h in p.read_text() for h in ('#include "rg_k_', '#include "rg_render_')))
 
