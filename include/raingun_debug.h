@@ -149,6 +149,18 @@ rg_status rg_debug_counter_words(const rg_scene *scene, int32_t first, int32_t n
  * kernel.  A word the launcher writes; results are identical either way. */
 rg_status rg_debug_last_plain(const rg_scene *scene, int32_t *plain);
 
+/* The PLAIN light kernels compute the camera ray's two quotients from host reciprocals and its
+ * length without range scaling, after the launcher has checked the frame size column by column and
+ * row by row and bounded the field of view.  rg_debug_set_exact_div(0): the scene's launches behave
+ * as if that check had failed, so they run the general kernel (1, the default: the check decides).
+ * Results are identical either way.
+ * rg_debug_camera_check: a small kernel computes the camera direction of every pixel of a
+ * width x height frame at `fov` degrees both ways; *mismatches = the pixels whose directions
+ * differ in any bit, *admitted (nullable) = 1 if the launcher's checks admit that frame, else 0. */
+rg_status rg_debug_set_exact_div(rg_scene *scene, int32_t enable);
+rg_status rg_debug_camera_check(const rg_scene *scene, uint32_t width, uint32_t height, double fov,
+                                uint64_t *mismatches, int32_t *admitted);
+
 #ifdef __cplusplus
 }
 #endif

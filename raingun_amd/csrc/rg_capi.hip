@@ -22,6 +22,7 @@
 #include "../../include/raingun.h"
 #include "../../include/raingun_debug.h"
 #include "rg_device.h"
+#include "rg_exact.h"
 #include "rg_internal.h"
 #include "rg_launchers.h"
 
@@ -546,6 +547,39 @@ rg_status rg_debug_last_plain(const rg_scene *s, int32_t *plain) {
     if (!s || !plain || !s->last) return RG_ERR_INVALID_ARGUMENT;
     *plain = s->last->last_plain;
     return RG_OK;
+}
+
+rg_status rg_debug_set_exact_div(rg_scene *s, int32_t enable) {
+    if (!s || (enable != 0 && enable != 1)) return RG_ERR_INVALID_ARGUMENT;
+    s->exact_div = enable != 0;
+    return RG_OK;
+}
+
+rg_status rg_debug_camera_check(const rg_scene *s, uint32_t width, uint32_t height, double fov, uint64_t *mismatches,
+                                int32_t *admitted) {
+    if (!s || !mismatches || width == 0 || height == 0 || (unsigned long long)width * height >= (1ull << 32))
+        return RG_ERR_INVALID_ARGUMENT;
+    if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
+    RgKernelArgs a = rg_make_args(s);
+    a.width = width;
+    a.height = height;
+    a.width_d = (double)width;
+    a.height_d = (double)height;
+    a.aspect = a.width_d / a.height_d;
+    a.fov_adjustment = rg_fov_adjustment(fov);
+    a.inv_w = 1.0 / a.width_d;
+    a.inv_h = 1.0 / a.height_d;
+    if (admitted)
+        *admitted = rg_recip_div_ok(width) && rg_recip_div_ok(height) && rg_camera_unscaled_ok(a.fov_adjustment, a.aspect);
+    unsigned long long *d_bad = nullptr, bad = 0;
+    if (!ok(hipMalloc(&d_bad, sizeof bad))) return RG_ERR_OUT_OF_MEMORY;
+    rg_status st = RG_OK;
+    if (!ok(hipMemset(d_bad, 0, sizeof bad)) || !ok(rg_launch_camera_check(&a, d_bad, nullptr)) ||
+        !ok(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost)))
+        st = RG_ERR_DEVICE;
+    (void)hipFree(d_bad);
+    *mismatches = bad;
+    return st;
 }
 
 rg_status rg_debug_counter_words(const rg_scene *s, int32_t first, int32_t n, uint64_t *out) {

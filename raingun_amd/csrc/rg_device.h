@@ -97,6 +97,14 @@ struct RgTexDev {
     int32_t w, h;
 };
 
+// PLAIN light kernels only (rg_k_shade.h), made by the host once per scene.
+struct RgTexMagic {        // per texture: the magic (rg_exact.h rg_magic_u32) of its width and of its height
+    uint32_t mw, shw, mh, shh;
+};
+struct RgPlnAxes {         // per body id, planes only (else zero): the texture axes of bodies.rs:155-169
+    double xa[3], ya[3];
+};
+
 // Everything a render launch needs, passed by value as the kernel argument.
 struct RgKernelArgs {
     // hot tables
@@ -215,6 +223,21 @@ struct RgKernelArgs {
     // the struct: the other instantiations keep their argument offsets.
     const uint8_t *px_mask;
     uint32_t tile_limit, px_k, px_w;
+    // The PLAIN light kernels' camera quotients (rg_exact.h rg_recip_quot): 1.0 / width_d and
+    // 1.0 / height_d.  plain_veto != 0: the launch runs the general kernel -- the residual form differs
+    // from the division for some column or row of this frame size (bit 0; also set by
+    // rg_debug_set_exact_div(0)), or there is no blob image (bit 1).  The launch context fills all three.
+    uint32_t plain_veto;
+    double inv_w, inv_h;
+    // The PLAIN light kernels' tile start: the magic (rg_exact.h rg_magic_u32) of the launch's tiles per
+    // row (8x8 tiles); log2 of tile_rows, or 32 where it is no power of two -- then its magic; and 1
+    // where output row, image row and the call's row are one and the same (tile_stride 1, tile_offset 0,
+    // tile_base 0, no groups, no split call), so that the kernel skips the mapping.
+    uint32_t tiles_x_m, tiles_x_sh, tile_rows_shift, tile_rows_m, tile_rows_sh, rows_identity;
+    // The PLAIN light kernels' two tables behind the arena [0, lds_total_bytes) in the blob image:
+    // texm[n_textures] parallel to texs, axes[n_bodies] by body id; the arena with them is
+    // [0, lds_plain_bytes), the LDS those kernels are launched with and stage.
+    uint32_t lds_texm, lds_axes, lds_plain_bytes;
 };
 
 __host__ __device__ inline uint32_t rg_tile_w(const RgKernelArgs &a) { return 1u << a.tile_wlog; }

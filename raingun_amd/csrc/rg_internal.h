@@ -66,6 +66,9 @@ struct rg_launch_ctx {
     size_t prim_cap = 0;     // bytes
     uint32_t prim_w = 0, prim_h = 0;
     double prim_fov = 0.0;
+    // the frame size whose camera quotients were last swept (rg_exact.h rg_recip_div_ok), and the verdict
+    uint32_t rdiv_w = 0, rdiv_h = 0;
+    bool rdiv_ok = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -184,6 +187,7 @@ struct rg_scene {
     int32_t lb_cam = -1;            // the camera buffer's index in lbuf (primary rays), -1: none
     int32_t n_lbdesc = 0;           // descriptors in lbuf (light slots + the camera buffer)
     bool lbuf_enabled = true;       // rg_debug_set_lightbuf
+    bool exact_div = true;          // rg_debug_set_exact_div: 0 = launches behave as if the quotient sweep had failed
     float bvh_obound = 0.0f;
     double bvh_rbound = 0.0, bvh_margin = 0.0, bvh_extent = 0.0;
     rg_bvh_info bvh_info{};
@@ -311,6 +315,8 @@ rg_status rg_grow(rg_mem kind, T *&p, size_t &cap, size_t bytes) {  // one buffe
     return rg_grow(kind, cap, bytes, {{p, bytes}});
 }
 
+// rg_scene.hip: RgKernelArgs::fov_adjustment of a field of view in degrees.
+double rg_fov_adjustment(double fov);
 // rg_scene.hip: is the scene on the heavy path (rg_device.h rg_heavy_path)?
 bool rg_scene_heavy(const rg_scene *s);
 // rg_scene.hip: the LDS arena of launch args `a` as one device image (light path:

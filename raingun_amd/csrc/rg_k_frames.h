@@ -107,6 +107,18 @@ __device__ __forceinline__ uint32_t out_row_to_y(const RgKernelArgs &a, uint32_t
     return y >= a.height ? 0xFFFFFFFFu : (uint32_t)y;
 }
 
+// The same (PLAIN kernels), with the host's shift where tile_rows is a power of two
+// (RgKernelArgs::tile_rows_shift; 32: it is not, so its magic, rg_exact.h).
+__device__ __forceinline__ uint32_t out_row_to_y_shift(const RgKernelArgs &a, uint32_t orow) {
+    const uint32_t tl = a.tile_rows_shift < 32u ? orow >> a.tile_rows_shift : rg_magic_div(orow, a.tile_rows_m, a.tile_rows_sh);
+    const uint32_t r = orow - tl * a.tile_rows;
+    const unsigned long long i = (unsigned long long)(tl + a.tile_base);
+    const unsigned long long ti = a.tile_group > 1u ? (i / a.tile_group) * a.tile_stride + a.tile_offset + i % a.tile_group
+                                                    : i * a.tile_stride + a.tile_offset;
+    unsigned long long y = ti * a.tile_rows + r;
+    return y >= a.height ? 0xFFFFFFFFu : (uint32_t)y;
+}
+
 // Output row of the launch's dense row `orow`: itself, or -- one launch of a call split over
 // several (RgKernelArgs::out_tile_mul > 1) -- the row of the CALL's selected tile
 // (orow / tile_rows) * mul + add that this launch's tile is.

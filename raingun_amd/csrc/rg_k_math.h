@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "rg_device.h"
+#include "rg_exact.h"
 
 #pragma clang fp contract(off)
 
@@ -31,6 +32,47 @@ __device__ __forceinline__ double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.
 __device__ __forceinline__ V3 normalize(V3 a) { return scl(a, 1.0 / sqrt(dot(a, a))); }
 __device__ __forceinline__ V3 cross(V3 a, V3 b) {
     return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+
+// sqrt(x) and 1.0 / m as hipcc expands them for gfx950 (v_rsq_f64 / v_rcp_f64 and the same fma
+// refinement, read off this tree's assembly), WITHOUT the range scaling in front (v_ldexp_f64,
+// v_div_scale_f64) and the special-case selects behind (v_cmp_class, v_div_fmas' scale,
+// v_div_fixup_f64): for operands the host has bounded (rg_exact.h rg_camera_unscaled_ok) every one
+// of those is the identity, so the bits are the expansion's.  10 and 7 instructions for 18 and 12.
+__device__ __forceinline__ double sqrt_unscaled(double x) {
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = y * 0.5;
+    const double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
+    return __builtin_fma(__builtin_fma(-g, g, x), h, g);
+}
+__device__ __forceinline__ double rcp_unscaled(double m) {
+    double r = __builtin_amdgcn_rcp(m);
+    r = __builtin_fma(r, __builtin_fma(-m, r, 1.0), r);
+    r = __builtin_fma(r, __builtin_fma(-m, r, 1.0), r);
+    // the quotient 1.0 * r is r; its residual, times r, on top (v_div_fmas_f64 without its scale)
+    return __builtin_fma(__builtin_fma(-m, r, 1.0), r, r);
+}
+
+// The primary ray's sensor coordinates (ray.rs:46-51) of pixel (x, y).  _div: the reference's two
+// divisions.  _recip (PLAIN kernels): the residual-form quotients of rg_exact.h with the host's
+// a.inv_w / a.inv_h, which the launcher admits only after rg_recip_div_ok has compared every
+// column's and row's quotient with the division (rg_render_launch.h rg_light_plain).
+__device__ __forceinline__ void sensor_div(const RgKernelArgs &a, uint32_t x, uint32_t y, double &sx, double &sy) {
+    sx = ((((double)x + 0.5) / a.width_d) * 2.0 - 1.0) * a.aspect * a.fov_adjustment;
+    sy = (1.0 - (((double)y + 0.5) / a.height_d) * 2.0) * a.fov_adjustment;
+}
+__device__ __forceinline__ void sensor_recip(const RgKernelArgs &a, uint32_t x, uint32_t y, double &sx, double &sy) {
+    sx = (rg_recip_quot(rg_pixel_centre(x), a.width_d, a.inv_w) * 2.0 - 1.0) * a.aspect * a.fov_adjustment;
+    sy = (1.0 - rg_recip_quot(rg_pixel_centre(y), a.height_d, a.inv_h) * 2.0) * a.fov_adjustment;
+}
+// normalize((sx, sy, -1)) (ray.rs:52-54) with the unscaled expansions: the operand is at least 1
+// and bounded by the launcher (rg_camera_unscaled_ok).
+__device__ __forceinline__ V3 normalize_camera(double sx, double sy) {
+    const V3 d = v3(sx, sy, -1.0);
+    return scl(d, rcp_unscaled(sqrt_unscaled(dot(d, d))));
 }
 
 __device__ __forceinline__ C3 c3(float r, float g, float b) { return C3{r, g, b}; }

@@ -100,6 +100,61 @@ __device__ __forceinline__ C3 texel_color(uint32_t px) {
     return c3(u8_div255(px & 0xffu), u8_div255((px >> 8) & 0xffu), u8_div255((px >> 16) & 0xffu));
 }
 
+// The textured hit of the PLAIN light kernels (no disks, no boxes: a body is a sphere or a plane).
+// RG_PLAIN_AXES: a plane's texture axes come from the host's table by body id (RgPlnAxes, rg_exact.h
+// rg_plane_axes: the expressions of texture_coords above) -- a subtraction and two dot products
+// remain of two cross products, a dot, a compare and a select.  RG_PLAIN_WRAP: material.rs:70-79
+// with the texture dimension's magic (RgTexMagic, rg_exact.h rg_wrap_i32) for the i32 % expansion.
+// 0: as the other kernels (A/B builds).
+#ifndef RG_PLAIN_AXES
+#define RG_PLAIN_AXES 1
+#endif
+#ifndef RG_PLAIN_WRAP
+#define RG_PLAIN_WRAP 1
+#endif
+struct PlainTex {
+    const RgTexMagic *texm;  // parallel to the texture descriptors
+    const RgPlnAxes *axes;   // by body id
+};
+__device__ __forceinline__ void texture_coords_plain(const PlainTex &P, const RgBodyDev &b, int id, V3 h, float &tx, float &ty) {
+#if RG_PLAIN_AXES
+    if (b.kind == RG_BODY_SPHERE) {
+        V3 hv = sub(h, bp3(b, 0));
+        const float2 uv = sphere_uv(hv.x, hv.y, hv.z, b.p[3]);
+        tx = uv.x;
+        ty = uv.y;
+    } else {
+        const RgPlnAxes A = P.axes[id];
+        V3 hv = sub(h, bp3(b, 0));
+        tx = (float)dot(hv, v3(A.xa[0], A.xa[1], A.xa[2]));
+        ty = (float)dot(hv, v3(A.ya[0], A.ya[1], A.ya[2]));
+    }
+#else
+    texture_coords(b, h, tx, ty);
+#endif
+}
+__device__ __forceinline__ uint32_t texel_fetch_plain(const RgTexDev *texs, const PlainTex &P, const RgMatDev &m,
+                                                       const RgBodyDev &b, int id, V3 h) {
+    float tx, ty;
+    texture_coords_plain(P, b, id, h, tx, ty);
+    const RgTexDev t = texs[m.tex];
+#if RG_PLAIN_WRAP
+    const RgTexMagic g = P.texm[m.tex];
+    uint32_t x = rg_wrap_i32(f32_to_i32((tx + m.xoff) * (float)t.w), (uint32_t)t.w, g.mw, g.shw);
+    uint32_t y = rg_wrap_i32(f32_to_i32((ty + m.yoff) * (float)t.h), (uint32_t)t.h, g.mh, g.shh);
+#else
+    uint32_t x = wrap(tx + m.xoff, t.w);
+    uint32_t y = wrap(ty + m.yoff, t.h);
+#endif
+    const __attribute__((address_space(1))) uint32_t *tg = (const __attribute__((address_space(1))) uint32_t *)t.texels;
+    return tg[(size_t)y * (uint32_t)t.w + x];
+}
+__device__ __forceinline__ C3 surface_color_plain(const RgTexDev *texs, const PlainTex &P, const RgMatDev &m,
+                                                  const RgBodyDev &b, int id, V3 h) {
+    if (m.coloration == RG_COLORATION_COLOR) return c3(m.color[0], m.color[1], m.color[2]);
+    return texel_color(texel_fetch_plain(texs, P, m, b, id, h));
+}
+
 // body.color(&body.texture_coords(hit)) (rendering.rs:134-135, 103).  The
 // texture coordinates are pure functions of the hit and only a Texture
 // coloration reads them, so they are computed for textured materials only:

@@ -44,6 +44,31 @@ __global__ __launch_bounds__(256) void rg_trace_kernel(RgKernelArgs a, const dou
     }
 }
 
+// rg_debug_camera_check: every pixel's camera direction as the general kernels compute it (two
+// divisions, normalize) and as the PLAIN kernels do (rg_k_math.h sensor_recip, normalize_camera);
+// *bad counts the pixels whose directions differ in any bit.  One lane per pixel; reads a.width,
+// a.height, the frame constants and a.inv_w / a.inv_h only.
+__global__ __launch_bounds__(256) void rg_camera_check_kernel(RgKernelArgs a, unsigned long long *bad) {
+    const unsigned long long p = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    if (p >= (unsigned long long)a.width * a.height) return;
+    const uint32_t y = (uint32_t)(p / a.width), x = (uint32_t)(p - (unsigned long long)y * a.width);
+    double sx, sy;
+    sensor_div(a, x, y, sx, sy);
+    const V3 d0 = normalize(v3(sx, sy, -1.0));
+    sensor_recip(a, x, y, sx, sy);
+    const V3 d1 = normalize_camera(sx, sy);
+    if (__double_as_longlong(d0.x) != __double_as_longlong(d1.x) || __double_as_longlong(d0.y) != __double_as_longlong(d1.y) ||
+        __double_as_longlong(d0.z) != __double_as_longlong(d1.z))
+        atomicAdd(bad, 1ull);
+}
+
+extern "C" hipError_t rg_launch_camera_check(const RgKernelArgs *a, unsigned long long *bad, hipStream_t stream) {
+    const unsigned long long n = (unsigned long long)a->width * a->height;
+    if (n == 0 || n >= (1ull << 32)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rg_camera_check_kernel, dim3((unsigned)((n + 255ull) / 256ull)), dim3(256), 0, stream, *a, bad);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- launchers
 // Occupancy of one kernel instantiation on the CURRENT device, cached per
 // (device, kernel, dynamic LDS): hipFuncSetAttribute and the occupancy query

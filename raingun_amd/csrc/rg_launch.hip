@@ -17,6 +17,7 @@
 #include "../../include/raingun.h"
 #include "../../include/raingun_debug.h"
 #include "rg_device.h"
+#include "rg_exact.h"
 #include "rg_internal.h"
 #include "rg_launchers.h"
 
@@ -59,7 +60,7 @@ rg_status validate(const rg_scene *s, const rg_launch_desc &d, uint32_t *out_row
 }
 
 // 2. The scene's arguments plus this launch's frame, tiling, outputs and counter sets.
-RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, const rg_launch_ctx *cx, uint32_t out_rows) {
+RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx *cx, uint32_t out_rows) {
     RgKernelArgs a = rg_make_args(s);
     a.counters = cx->counters + (size_t)cx->cur * RG_COUNTER_WORDS;  // zero (see rg_launch_ctx::counters)
     a.counters_next = cx->counters + (size_t)(1 - cx->cur) * RG_COUNTER_WORDS;
@@ -75,6 +76,16 @@ RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, const rg_laun
     a.aspect = (double)d.width / (double)d.height;
     a.width_d = (double)d.width;
     a.height_d = (double)d.height;
+    // the PLAIN kernels' camera quotients (rg_exact.h): every column and row of a frame size swept
+    // once per launch context (n divisions for n pixels a side), then remembered
+    if (cx->rdiv_w != d.width || cx->rdiv_h != d.height) {
+        cx->rdiv_ok = rg_recip_div_ok(d.width) && rg_recip_div_ok(d.height);
+        cx->rdiv_w = d.width;
+        cx->rdiv_h = d.height;
+    }
+    a.inv_w = 1.0 / a.width_d;
+    a.inv_h = 1.0 / a.height_d;
+    a.plain_veto = (cx->rdiv_ok && s->exact_div) ? 0u : 1u;
     a.rgba = reinterpret_cast<uint32_t *>(d.rgba);
     a.rgb = d.rgb;
     a.tile_flags = d.tile_flags;
@@ -96,6 +107,19 @@ RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, const rg_laun
         a.ring_flush = (uint32_t)std::max(0, big ? s->ring_flush_big : s->ring_flush_small);
         a.ring_group = (uint32_t)std::max(0, big ? s->ring_group_big : s->ring_group_small);
     }
+    // the PLAIN kernels' tile start (RgKernelArgs::tiles_x_m ..): divisions by launch constants
+    const RgMagicU32 mx = rg_magic_u32(rg_tiles_x(a)), mr = rg_magic_u32(a.tile_rows);
+    a.tiles_x_m = mx.m;
+    a.tiles_x_sh = mx.sh;
+    a.tile_rows_m = mr.m;
+    a.tile_rows_sh = mr.sh;
+    a.tile_rows_shift = 32u;
+    for (uint32_t k = 0; k < 32u; ++k)
+        if (a.tile_rows == 1u << k) a.tile_rows_shift = k;
+    a.rows_identity = (a.tile_stride == 1u && a.tile_offset == 0u && a.tile_base == 0u && a.tile_group <= 1u &&
+                       a.out_tile_mul <= 1u)
+                          ? 1u
+                          : 0u;
     return a;
 }
 
@@ -300,7 +324,10 @@ rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_
     const int disp = ((d.host_frame && !host_arrays) || d.px_mask) ? std::max(frames, rg_max_array_frames() + 1) : frames;
     if ((st = size_deep_frames(cx, a, frames, disp)) != RG_OK) return st;
     if ((st = refresh_prim_table(cx, a, d.stream)) != RG_OK) return st;
-    if (!rg_heavy_path(a)) a.lds_blob = rg_lds_blob_for(s, a);  // light path: one staging loop per block
+    if (!rg_heavy_path(a)) {  // light path: one staging loop per block
+        a.lds_blob = rg_lds_blob_for(s, a);
+        if (!a.lds_blob) a.plain_veto |= 2u;  // the PLAIN kernels' two tables exist in the image only
+    }
     if (d.timed && !ok(hipEventRecord(cx->ev0, d.stream))) return RG_ERR_DEVICE;  // kernel_ms includes the tile probe
     // a sparse launch's list only schedules: no probe, and the cached order and its key stay as they are
     if (!d.px_mask && (st = order_tiles(s, d, cx, a)) != RG_OK) return st;

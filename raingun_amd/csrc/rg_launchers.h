@@ -20,6 +20,9 @@ extern "C" hipError_t rg_launch_resolve(const float *in, uint32_t width, uint32_
                                         float *rgb, hipStream_t stream);
 extern "C" hipError_t rg_launch_trace(const RgKernelArgs *a, const double *rays, uint32_t n, double *dist,
                                       int32_t *body, hipStream_t stream);
+// rg_kernels.hip: *bad (device, zeroed by the caller) += the pixels of the a->width x a->height frame whose
+// camera direction differs between the general and the PLAIN kernels' arithmetic (rg_debug_camera_check).
+extern "C" hipError_t rg_launch_camera_check(const RgKernelArgs *a, unsigned long long *bad, hipStream_t stream);
 // rg_resolve.hip: the resolve of adaptive anti-aliasing over rows x width output pixels: pixels
 // whose mask byte is non-zero become the box resolve of their k x k samples of `in` (nullable:
 // none), the others keep rgba and get their rgb (nullable) clamped in place.

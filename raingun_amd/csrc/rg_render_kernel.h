@@ -47,6 +47,16 @@ using namespace rgk;
 #endif
 #define RG_QUEUE_BASE 16   // counters[16 + 16*q]: head q, one 128-B line each
 #define RG_QUEUE_STRIDE 16
+// What the PLAIN kernels do without the reference's divisions (0: as the other kernels, for
+// A/B builds): the camera ray from host reciprocals and unscaled sqrt / reciprocal; the tile start
+// from the host's magic of tiles per row, a shift for tile_rows and no row mapping where it is the
+// identity.  (RG_PLAIN_WRAP and RG_PLAIN_AXES, the textured hit's two: rg_k_shade.h.)
+#ifndef RG_PLAIN_CAMERA
+#define RG_PLAIN_CAMERA 1
+#endif
+#ifndef RG_PLAIN_TILE
+#define RG_PLAIN_TILE 1
+#endif
 
 // Per-launch view of the cold (shading) tables: LDS copies or global.
 struct Cold {
@@ -75,6 +85,8 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
 // PLAIN (LDS-blob light kernels with array frames only): the launcher has checked (rg_render_launch.h
 // rg_light_plain) that the scene has no disks and no boxes, that a.rgb, a.tile_perm and a.lbuf are null,
 // that a.nan_scene is 0 and that a.n_lights == LB, so the kernel holds them as compile-time facts.
+// It has also checked what lets a PLAIN kernel replace divisions by launch constants with exact forms
+// (rg_exact.h): the camera quotients of this frame size, the camera ray's range, the blob image.
 // SPARSE (MAXD == 0 only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
 // renders its pixel only where a.px_mask says so (adaptive anti-aliasing, rg_aa.hip; RgKernelArgs::px_mask).
 template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
@@ -105,7 +117,7 @@ void rg_render_kernel(RgKernelArgs a) {
     if (blob) {
         const uint4 *g = reinterpret_cast<const uint4 *>(a.lds_blob);
         uint4 *d = reinterpret_cast<uint4 *>(smem);
-        const uint32_t n16 = a.lds_total_bytes / 16u;
+        const uint32_t n16 = (PLAIN ? a.lds_plain_bytes : a.lds_total_bytes) / 16u;  // PLAIN: with its two tables
         // four loads in flight per lane: unconditional (indices clamped into the image), then
         // the guarded LDS stores -- no per-lane array, which hipcc placed in scratch
         const uint32_t last = n16 - 1u;
@@ -180,6 +192,10 @@ void rg_render_kernel(RgKernelArgs a) {
         T.lights = a.lights;
         T.texs = a.texs;
     }
+    // PLAIN: the texture dimensions' magics and the planes' texture axes, behind the arena in the blob
+    // image (the launcher runs a PLAIN kernel only with the image: rg_launch.hip)
+    [[maybe_unused]] const PlainTex PT{reinterpret_cast<const RgTexMagic *>(smem + a.lds_texm),
+                                       reinterpret_cast<const RgPlnAxes *>(smem + a.lds_axes)};
     if (TASKS || LSPH || LCOLD) {
         if constexpr (TASKS) pool_init();
         __syncthreads();
@@ -348,7 +364,7 @@ void rg_render_kernel(RgKernelArgs a) {
                                 else if (b.kind != RG_BODY_AABB) RG_REGION(RGR_UV_PLANE);
                             }
 #endif
-                            if (textured) texel = texel_fetch(T.texs, m, b, h);
+                            if (textured) texel = PLAIN ? texel_fetch_plain(T.texs, PT, m, b, c.id, h) : texel_fetch(T.texs, m, b, h);
                             else { park[64 * PK_COL] = m.color[0]; park[64 * (PK_COL + 1)] = m.color[1]; park[64 * (PK_COL + 2)] = m.color[2]; }
                             park[64 * PK_REFL] = m.albedo_pi;                       // rendering.rs:164
                             // how the batch's colour is used: 0 diffuse, 1 reflecting at the depth
@@ -400,7 +416,7 @@ void rg_render_kernel(RgKernelArgs a) {
                     } else {
                         RG_REGION(RGR_REFRACT);
                         float kr = (float)fresnel(q.d, n, m.index);
-                        C3 surf = surface_color(T.texs, m, b, h);
+                        C3 surf = PLAIN ? surface_color_plain(T.texs, PT, m, b, c.id, h) : surface_color(T.texs, m, b, h);
                         int cd = qdepth + 1;
                         if (cd >= max_depth) {
                             // the transmission ray's unwrap (rendering.rs:106) precedes cast_ray's depth test
@@ -758,7 +774,9 @@ void rg_render_kernel(RgKernelArgs a) {
                 ++wt_tiles;
 #endif
                 if constexpr (K::host_frames) my_tile = tile;
-                const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+                constexpr bool fast_tile = PLAIN && RG_PLAIN_TILE != 0;
+                const uint32_t ty = fast_tile ? rg_magic_div(tile, a.tiles_x_m, a.tiles_x_sh) : tile / tiles_x;
+                const uint32_t tx = tile - ty * tiles_x;
 #ifdef RG_TILE_TIMES
                 cur_tile = tile;
                 t_tile = wall_clock64();
@@ -768,8 +786,14 @@ void rg_render_kernel(RgKernelArgs a) {
                 const uint32_t x = (tx << twlog) + ((uint32_t)lane & twmask);
                 const uint32_t orow = ty * th + ((uint32_t)lane >> twlog);
                 bool alive = x < a.width && orow < a.out_rows;
-                const uint32_t y = alive ? out_row_to_y(a, orow) : 0u;
-                oidx = (K::host_frames && !alive) ? RG_NO_PIXEL : (size_t)out_row_of(a, orow) * a.width + x;
+                uint32_t y;
+                if (fast_tile && a.rows_identity) {  // (wave-uniform) whole frames: every row is its own image row
+                    y = alive ? (orow >= a.height ? 0xFFFFFFFFu : orow) : 0u;
+                    oidx = (size_t)orow * a.width + x;
+                } else {
+                    y = alive ? (fast_tile ? out_row_to_y_shift(a, orow) : out_row_to_y(a, orow)) : 0u;
+                    oidx = (K::host_frames && !alive) ? RG_NO_PIXEL : (size_t)out_row_of(a, orow) * a.width + x;
+                }
                 if (K::host_frames && a.image_rows && alive)  // the whole image: the pixel's own row (padding: no store)
                     oidx = y == 0xFFFFFFFFu ? RG_NO_PIXEL : (size_t)y * a.width + x;
                 if (alive && y == 0xFFFFFFFFu) {  // padding row of a partial last tile
@@ -789,15 +813,20 @@ void rg_render_kernel(RgKernelArgs a) {
                     // heavy path: the host's per-column / per-row table of the same expressions
                     // (north star -1 %); the light path keeps the divisions (the loads at the
                     // tile's start cost it more than they save: test1 +0.5 %, test3 +1.5 %)
-                    if (!K::light && a.prim_sx) {
+                    // PLAIN: neither -- the quotients from the host's reciprocals and the ray's
+                    // length without range scaling, both admitted by the launcher (rg_light_plain)
+                    constexpr bool fast_camera = PLAIN && RG_PLAIN_CAMERA != 0;
+                    if constexpr (fast_camera) {
+                        sensor_recip(a, x, y, sx, sy);
+                    } else if (!K::light && a.prim_sx) {
                         sx = a.prim_sx[x];
                         sy = a.prim_sy[y];
                     } else {
-                        sx = ((((double)x + 0.5) / a.width_d) * 2.0 - 1.0) * a.aspect * a.fov_adjustment;
-                        sy = (1.0 - (((double)y + 0.5) / a.height_d) * 2.0) * a.fov_adjustment;
+                        sensor_div(a, x, y, sx, sy);
                     }
                     q.o = v3(0.0, 0.0, 0.0);
-                    q.d = normalize(v3(sx, sy, -1.0));
+                    if constexpr (fast_camera) q.d = normalize_camera(sx, sy);
+                    else q.d = normalize(v3(sx, sy, -1.0));
                     n_prim++;
                     closest_init(c);
                     trace_primary<F32F, BVH, PLAIN>(a, src, q.d, c);

@@ -13,6 +13,7 @@
 #include <cstddef>
 
 #include "rg_device.h"
+#include "rg_exact.h"
 #include "rg_render_cfg.h"
 #include "rg_render_grid.h"
 #include "rg_render_kernel.h"
@@ -129,17 +130,23 @@ static inline int rg_light_batch(int n_lights) {
 // May a device-resident light launch run the PLAIN instantiation of its kernel (rg_render_kernel.h)?  Every
 // fact that kernel holds at compile time, checked here: no disks and no boxes, no f32 RGB output, no
 // tile order, no light buffers, no NaN-scene path, a shadow batch exactly as wide as the scene's light
-// count -- and the whole scene in LDS (the PLAIN kernels are LSPH && LCOLD ones).
+// count -- and the whole scene in LDS (the PLAIN kernels are LSPH && LCOLD ones).  And what their
+// camera ray relies on (rg_exact.h): the launch context's sweep of this frame size found the
+// reciprocal form of the camera quotients equal to the division for every column and row,
+// and it has the arena's device image with their two tables (plain_veto: a word it writes, not the
+// frame's size), and the ray's squared length stays in the range where sqrt and the reciprocal need
+// no scaling.
 static inline bool rg_light_plain(const RgKernelArgs &a) {
     return a.n_dsk == 0 && a.n_box == 0 && a.rgb == nullptr && a.tile_perm == nullptr && a.lbuf == nullptr &&
-           a.nan_scene == 0 && a.n_lights == rg_light_batch(a.n_lights) && a.lds_total_bytes <= RG_LDS_BUDGET;
+           a.nan_scene == 0 && a.n_lights == rg_light_batch(a.n_lights) && a.lds_total_bytes <= RG_LDS_BUDGET &&
+           a.lds_plain_bytes <= RG_LDS_BUDGET && a.plain_veto == 0 && rg_camera_unscaled_ok(a.fov_adjustment, a.aspect);
 }
 
 // One light launch: the PLAIN kernel where the launch admits it (array frames only), else launch_waves' choice.
 template <class K>
 static hipError_t launch_light_one(const RgKernelArgs *a, hipStream_t stream, size_t *gt, bool plain) {
     if constexpr (!K::global_frames)
-        if (plain) return launch_one<typename K::plain>(a, a->lds_total_bytes, stream, gt);
+        if (plain) return launch_one<typename K::plain>(a, a->lds_plain_bytes, stream, gt);  // with its two tables
     return launch_waves<K>(a, stream, gt);
 }
 

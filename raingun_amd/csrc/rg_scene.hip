@@ -16,6 +16,7 @@
 #include "../../include/raingun_debug.h"
 #include "rg_bvh.h"
 #include "rg_device.h"
+#include "rg_exact.h"
 #include "rg_lightbuf.h"
 #include "rg_internal.h"
 
@@ -226,6 +227,10 @@ RgKernelArgs rg_make_args(const rg_scene *s) {
     a.lds_hot_bytes = a.lds_bodies;
     a.lds_mats = a.lds_bodies + (uint32_t)s->n_bodies * (uint32_t)sizeof(RgBodyDev);
     a.lds_total_bytes = a.lds_mats + (uint32_t)s->n_bodies * (uint32_t)sizeof(RgMatDev);
+    // behind the arena, in the blob image only: the PLAIN light kernels' tables (rg_device.h)
+    a.lds_texm = a.lds_total_bytes;
+    a.lds_axes = a.lds_texm + (uint32_t)s->n_textures * (uint32_t)sizeof(RgTexMagic);
+    a.lds_plain_bytes = a.lds_axes + (uint32_t)s->n_bodies * (uint32_t)sizeof(RgPlnAxes);
     a.def[0] = s->def[0];
     a.def[1] = s->def[1];
     a.def[2] = s->def[2];
@@ -234,6 +239,8 @@ RgKernelArgs rg_make_args(const rg_scene *s) {
     a.tile_wlog = 3;  // 8x8 tiles
     return a;
 }
+
+double rg_fov_adjustment(double fov) { return fov_adjustment(fov); }
 
 bool rg_scene_heavy(const rg_scene *s) {
     RgKernelArgs a;  // only what rg_heavy_path reads
@@ -255,9 +262,10 @@ const void *rg_lds_blob_for(const rg_scene *s, const RgKernelArgs &a) {
                                  (uint32_t)a.n_nodes, (uint32_t)a.n_sph};
     rg_scene *m = const_cast<rg_scene *>(s);
     if (m->lds_blob && std::memcmp(layout, m->lds_blob_layout, sizeof layout) == 0) return m->lds_blob;
-    if (!s->host || a.lds_total_bytes == 0 || a.lds_total_bytes % 16u != 0u) return nullptr;
+    if (!s->host || a.lds_total_bytes == 0 || a.lds_total_bytes % 16u != 0u || a.lds_plain_bytes % 16u != 0u)
+        return nullptr;
     const rg_host_tables &h = *s->host;
-    std::vector<unsigned char> img(a.lds_total_bytes, 0);
+    std::vector<unsigned char> img(a.lds_plain_bytes, 0);
     auto put = [&](uint32_t off, const void *src, size_t bytes) {
         if (bytes && off + bytes <= img.size()) std::memcpy(img.data() + off, src, bytes);
     };
@@ -274,6 +282,19 @@ const void *rg_lds_blob_for(const rg_scene *s, const RgKernelArgs &a) {
     put(a.lds_lights, h.lights.data(), h.lights.size() * sizeof(RgLightDev));
     put(a.lds_texs, s->tex_desc.data(), s->tex_desc.size() * sizeof(RgTexDev));
     if (a.lbuf) put(a.lds_lbuf, h.lbuf.data(), h.lbuf.size() * sizeof(RgLightBufDev));
+    // the PLAIN light kernels' tables: each texture dimension's magic, each plane's texture axes
+    std::vector<RgTexMagic> texm(h.tex_w.size(), RgTexMagic{0, 0, 0, 0});
+    for (size_t t = 0; t < texm.size(); ++t) {
+        if (h.tex_w[t] == 0 || h.tex_h[t] == 0) continue;
+        const RgMagicU32 mw = rg_magic_u32(h.tex_w[t]), mh = rg_magic_u32(h.tex_h[t]);
+        texm[t] = RgTexMagic{mw.m, mw.sh, mh.m, mh.sh};
+    }
+    put(a.lds_texm, texm.data(), texm.size() * sizeof(RgTexMagic));
+    std::vector<RgPlnAxes> axes(h.bodies.size());
+    std::memset(axes.data(), 0, axes.size() * sizeof(RgPlnAxes));
+    for (size_t b = 0; b < axes.size(); ++b)
+        if (h.bodies[b].kind == RG_BODY_PLANE) rg_plane_axes(&h.bodies[b].p[3], axes[b].xa, axes[b].ya);
+    put(a.lds_axes, axes.data(), axes.size() * sizeof(RgPlnAxes));
     void *p = nullptr;
     if (!ok(hipMalloc(&p, img.size()))) { (void)hipGetLastError(); return nullptr; }
     if (!ok(hipMemcpy(p, img.data(), img.size(), hipMemcpyHostToDevice))) { (void)hipFree(p); return nullptr; }
@@ -310,6 +331,7 @@ void rg_sync_settings(rg_scene *dst, const rg_scene *src) {
     dst->path = src->path;
     dst->bvh_enabled = src->bvh_enabled;
     dst->lbuf_enabled = src->lbuf_enabled;
+    dst->exact_div = src->exact_div;
     dst->lane_min_depth = src->lane_min_depth;
     dst->tile_order = src->tile_order;
     dst->ring_flush_small = src->ring_flush_small;

@@ -320,6 +320,19 @@ class DeviceScene:
         _abi.check(_abi.lib().rg_debug_last_plain(self.handle, C.byref(plain)))
         return plain.value == 1
 
+    def set_exact_div(self, enable: bool) -> None:
+        """False: launches behave as if the PLAIN kernels' camera-quotient check had failed, so they run
+        the general kernel (include/raingun_debug.h rg_debug_set_exact_div)."""
+        _abi.check(_abi.lib().rg_debug_set_exact_div(self.handle, 1 if enable else 0))
+
+    def camera_check(self, width: int, height: int, fov: float):
+        """rg_debug_camera_check: (pixels whose camera direction differs between the general and the
+        PLAIN kernels' arithmetic, whether the launcher's checks admit that frame)."""
+        bad, admitted = C.c_uint64(0), C.c_int32(-1)
+        _abi.check(_abi.lib().rg_debug_camera_check(self.handle, int(width), int(height), float(fov), C.byref(bad),
+                                                    C.byref(admitted)))
+        return int(bad.value), admitted.value == 1
+
     def bvh_info(self) -> _abi.rg_bvh_info:
         info = _abi.rg_bvh_info()
         _abi.check(_abi.lib().rg_debug_bvh_info(self.handle, C.byref(info)))
