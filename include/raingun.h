@@ -165,6 +165,33 @@ void rg_scene_destroy(rg_scene *scene);
  * the depth-5 configs set it directly, scene.rs:16 is a pub field). */
 rg_status rg_scene_set_max_depth(rg_scene *scene, uint32_t max_recursion_depth);
 
+/* A movable camera: the eye point and the basis the primary rays are built on.  For pixel (x, y)
+ * of a width x height frame, with sx, sy the reference's sensor coordinates (ray.rs:43-51):
+ *   D.k = (right.k * sx + up.k * sy) + forward.k     (k = x, y, z; f64, in this order, unfused)
+ *   ray = Ray::new(eye, normalize(D))                a primary ray at depth 0
+ * Every member finite, forward not all zero; the basis need be neither unit nor orthogonal.
+ * {eye 0, right (1,0,0), up (0,1,0), forward (0,0,-1)} is the reference's Ray::create_prime
+ * (ray.rs:37-54) bit for bit. */
+typedef struct rg_camera {
+    double eye[3], right[3], up[3], forward[3];
+} rg_camera;
+
+/* forward = normalize(target - eye), right = normalize(cross(forward, up)), up = cross(right,
+ * forward).  Pure host code.  RG_ERR_INVALID_ARGUMENT for a null pointer, target == eye, a
+ * non-finite input, cross(forward, up) == 0 or a result that is no camera. */
+rg_status rg_camera_look_at(const double eye[3], const double target[3], const double up[3], rg_camera *out);
+
+/* The camera of every later render of `scene` that goes through the tiled launch: rg_render_image,
+ * rg_render_tiles / _async / _pipelined, rg_render_stream, rg_render_image_aa / rg_render_aa_async,
+ * rg_render_image_aa_adaptive / rg_render_aa_adaptive, rg_render_multi (both modes; its replicas
+ * follow) and rg_frames_*.  rg_trace is unaffected; error codes and error_pixel keep their meaning.
+ * NULL restores the reference's view, and with it exactly the kernels the scene launched before.
+ * The camera is host state: it is read when a launch is enqueued and travels by value in the
+ * kernel's arguments, so changing it between launches on different streams needs no
+ * synchronisation and launches in flight keep theirs.  RG_ERR_INVALID_ARGUMENT for a non-finite
+ * member or a zero forward (the scene keeps the camera it had). */
+rg_status rg_scene_set_camera(rg_scene *scene, const rg_camera *camera);
+
 /* Blocking whole-frame render into a caller-owned host buffer of
  * width*height*4 bytes (row-major RGBA8, alpha 255).
  * Replaces rendering::render_image (rendering.rs:24-38). `stats` may be NULL.

@@ -109,6 +109,11 @@ class rg_tiling(C.Structure):
     _fields_ = [("tile_rows", C.c_uint32), ("tile_stride", C.c_uint32), ("tile_offset", C.c_uint32)]
 
 
+class rg_camera(C.Structure):
+    _fields_ = [("eye", C.c_double * 3), ("right", C.c_double * 3), ("up", C.c_double * 3),
+                ("forward", C.c_double * 3)]
+
+
 class rg_bvh_info(C.Structure):  # include/raingun_debug.h
     _fields_ = [("built", C.c_int32), ("enabled", C.c_int32), ("nodes", C.c_int32), ("leaves", C.c_int32),
                 ("depth", C.c_int32), ("margin", C.c_float), ("origin_bound", C.c_float), ("lane_stack", C.c_int32),
@@ -143,6 +148,8 @@ EXPORTED_SYMBOLS = (
     "rg_render_image_aa_adaptive",
     "rg_render_aa_adaptive",
     "rg_edge_mask",
+    "rg_camera_look_at",
+    "rg_scene_set_camera",
 )
 # include/raingun_debug.h
 DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "rg_debug_counters",
@@ -183,6 +190,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.rg_scene_destroy.argtypes = [C.c_void_p]
     lib.rg_scene_set_max_depth.restype = C.c_int32
     lib.rg_scene_set_max_depth.argtypes = [C.c_void_p, C.c_uint32]
+    lib.rg_camera_look_at.restype = C.c_int32
+    lib.rg_camera_look_at.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), P(rg_camera)]
+    lib.rg_scene_set_camera.restype = C.c_int32
+    lib.rg_scene_set_camera.argtypes = [C.c_void_p, P(rg_camera)]
     lib.rg_render_image.restype = C.c_int32
     lib.rg_render_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, P(rg_stats)]
     lib.rg_render_tiles_async.restype = C.c_int32

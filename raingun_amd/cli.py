@@ -1,6 +1,7 @@
 """`raingun` command line, mirroring the reference's src/main.rs + src/render.rs.
 
-    python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T] [-o FILE] FILE
+    python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
+                              [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
@@ -12,7 +13,11 @@ pixel on the regular sub-pixel grid and box-filters them (rg_render_image_aa);
 --draft leaves it alone.  `--adaptive T` (0..256; not in the reference) spends
 the N x N rays only on pixels whose 8-neighbourhood contrast in the 1-sample
 frame is at least T (rg_render_image_aa_adaptive); with --samples 1 it is
-accepted and has no effect.  The
+accepted and has no effect.  `--eye X,Y,Z --look-at X,Y,Z [--up X,Y,Z]` (not in
+the reference, whose view is from the origin down -z) move the camera
+(rg_scene_set_camera): --up defaults to 0,1,0, --eye without --look-at looks
+down -z from the eye; a malformed triple or a rejected look-at ends the run
+like any other bad flag value.  The scene file has no camera key.  The
 render itself runs on the GPU (rg_render_image); the scene is loaded and the
 PNG written by the native host layer (libraingun_host.so), and the timing line matches
 print_render_message (render.rs:218-244).  `--preview` (piston window) is not
@@ -29,6 +34,8 @@ from typing import List, Optional
 
 import numpy as np
 
+from .camera import Camera, camera_from_flags, parse_triple
+
 
 @dataclass
 class RenderOptions:          # render.rs:32-46
@@ -37,6 +44,7 @@ class RenderOptions:          # render.rs:32-46
     max_recursion_depth: Optional[int] = None
     samples: int = 1          # N x N rays per pixel (--samples; not in the reference)
     adaptive: Optional[int] = None  # contrast threshold of adaptive anti-aliasing (--adaptive)
+    camera: Optional[Camera] = None  # --eye / --look-at / --up (not in the reference)
 
 
 class _LastWins(argparse.Action):
@@ -68,6 +76,10 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("--adaptive", metavar="T",
                    help="Adaptive anti-aliasing: the N x N rays only where the 8-neighbourhood contrast of the "
                         "1-sample frame is at least T (0..256).")
+    p.add_argument("--eye", metavar="X,Y,Z", help="Camera position (default 0,0,0).")
+    p.add_argument("--look-at", dest="look_at", metavar="X,Y,Z",
+                   help="Point the camera looks at (default: straight down -z from the eye).")
+    p.add_argument("--up", metavar="X,Y,Z", help="Up hint of --look-at (default 0,1,0).")
     p.add_argument("input", metavar="FILE", help="The scene definition file, in YAML format.")
     return p
 
@@ -82,6 +94,7 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
         o.adaptive = _parse_u32(ns.adaptive, "Could not parse adaptive")
         if not 0 <= o.adaptive <= 256:
             raise SystemExit("adaptive must be between 0 and 256")
+    o.camera = _parse_camera(ns)
     if ns.draft:
         o.max_recursion_depth = 4
     elif ns.hd:
@@ -97,6 +110,20 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
     return o
 
 
+def _parse_camera(ns: argparse.Namespace) -> Optional[Camera]:
+    triples = {}
+    for flag in ("eye", "look_at", "up"):
+        text = getattr(ns, flag, None)
+        try:
+            triples[flag] = None if text is None else parse_triple(text)
+        except ValueError:
+            raise SystemExit(f"Could not parse {flag.replace('_', '-')}") from None
+    try:
+        return camera_from_flags(triples["eye"], triples["look_at"], triples["up"])
+    except ValueError as e:
+        raise SystemExit(f"Could not build the camera: {e}") from None
+
+
 def _parse_u32(s: str, msg: str) -> int:
     try:
         v = int(s, 10)
@@ -107,8 +134,24 @@ def _parse_u32(s: str, msg: str) -> int:
     return v
 
 
+def _join_triples(args: Optional[List[str]]) -> List[str]:
+    """`--eye -1,2,3` -> `--eye=-1,2,3`: argparse would read a triple that starts with a minus sign as
+    an unknown option."""
+    if args is None:
+        args = sys.argv[1:]
+    out: List[str] = []
+    it = iter(args)
+    for a in it:
+        if a in ("--eye", "--look-at", "--up"):
+            v = next(it, None)
+            out.append(a if v is None else f"{a}={v}")
+        else:
+            out.append(a)
+    return out
+
+
 def parse_arguments(args: List[str]) -> RenderOptions:
-    return options_from(construct_app().parse_args(args))
+    return options_from(construct_app().parse_args(_join_triples(args)))
 
 
 # ---------------------------------------------------------------- PNG (RGBA8)
@@ -130,7 +173,7 @@ def format_duration(ms: int) -> str:  # render.rs:229-244
 
 
 def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
-    ns = construct_app().parse_args(argv)
+    ns = construct_app().parse_args(_join_triples(argv))
     opts = options_from(ns)
     if ns.preview:
         print("--preview is not supported on this build (no display); rendering without preview",
@@ -155,6 +198,7 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
     from .scene import DeviceScene
 
     ds = DeviceScene(scene, device=ns.gpu)
+    ds.set_camera(opts.camera)
     t0 = time.perf_counter()                     # render.rs:54-56
     if opts.samples > 1 and opts.adaptive is not None:
         img = ds.render_image_aa_adaptive(opts.width, opts.height, opts.samples, opts.adaptive)

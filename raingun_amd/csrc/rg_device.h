@@ -226,7 +226,8 @@ struct RgKernelArgs {
     // The PLAIN light kernels' camera quotients (rg_exact.h rg_recip_quot): 1.0 / width_d and
     // 1.0 / height_d.  plain_veto != 0: the launch runs the general kernel -- the residual form differs
     // from the division for some column or row of this frame size (bit 0; also set by
-    // rg_debug_set_exact_div(0)), or there is no blob image (bit 1).  The launch context fills all three.
+    // rg_debug_set_exact_div(0)), or there is no blob image (bit 1), or the launch has a camera (bit 2).
+    // The launch context fills all three.
     uint32_t plain_veto;
     double inv_w, inv_h;
     // The PLAIN light kernels' tile start: the magic (rg_exact.h rg_magic_u32) of the launch's tiles per
@@ -238,6 +239,13 @@ struct RgKernelArgs {
     // texm[n_textures] parallel to texs, axes[n_bodies] by body id; the arena with them is
     // [0, lds_plain_bytes), the LDS those kernels are launched with and stage.
     uint32_t lds_texm, lds_axes, lds_plain_bytes;
+    // The launch's camera (rg_camera.h; rg_scene_set_camera), by value: camera != 0 selects the camera
+    // family of rg_render_kernel (rg_render_cfg.h RG_MAXD_CAMERA), whose primary rays leave cam_eye
+    // towards normalize((cam_right * sx + cam_up * sy) + cam_forward).  0: the reference's view from
+    // the origin down -z, and the other members are not read.  At the end of the struct: the other
+    // instantiations keep their argument offsets.
+    uint32_t camera;
+    double cam_eye[3], cam_right[3], cam_up[3], cam_forward[3];
 };
 
 __host__ __device__ inline uint32_t rg_tile_w(const RgKernelArgs &a) { return 1u << a.tile_wlog; }

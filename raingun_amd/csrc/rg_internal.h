@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstring>
 #include <initializer_list>
 #include <memory>
 #include <vector>
@@ -50,7 +51,10 @@ struct rg_launch_ctx {
             tile_group;
         double fov;
         const void *mats;
+        bool camera = false;  // the launch's camera (RgKernelArgs::camera, cam_eye .. cam_forward), zero without one
+        double cam[12] = {};
         bool operator==(const PermKey &o) const {
+            if (camera != o.camera || std::memcmp(cam, o.cam, sizeof cam) != 0) return false;
             return width == o.width && height == o.height && tile_rows == o.tile_rows && tile_stride == o.tile_stride &&
                    tile_offset == o.tile_offset && tile_base == o.tile_base && out_rows == o.out_rows &&
                    tile_group == o.tile_group &&
@@ -188,6 +192,10 @@ struct rg_scene {
     int32_t n_lbdesc = 0;           // descriptors in lbuf (light slots + the camera buffer)
     bool lbuf_enabled = true;       // rg_debug_set_lightbuf
     bool exact_div = true;          // rg_debug_set_exact_div: 0 = launches behave as if the quotient sweep had failed
+    // rg_scene_set_camera: host state, read when a launch is enqueued and passed by value in its kernel
+    // arguments (RgKernelArgs::camera ..), so launches in flight keep the camera they were enqueued with
+    bool has_camera = false;
+    rg_camera camera{};
     float bvh_obound = 0.0f;
     double bvh_rbound = 0.0, bvh_margin = 0.0, bvh_extent = 0.0;
     rg_bvh_info bvh_info{};

@@ -122,9 +122,9 @@ static bool host_frame_launch(const RgKernelArgs *a) {
 }
 
 // Does this launch keep its frames in the launch context's global buffer (the
-// host sizes it with rg_render_grid_threads)?  Depths above the arrays.
+// host sizes it with rg_render_grid_threads)?  Depths above the arrays, sparse and camera launches.
 extern "C" int rg_launch_global_frames(const RgKernelArgs *a, int maxd) {
-    return a->px_mask != nullptr || maxd > rg_max_array_frames();
+    return a->px_mask != nullptr || a->camera != 0 || maxd > rg_max_array_frames();
 }
 
 template <int MAXD, bool HF = false>
@@ -139,6 +139,13 @@ static hipError_t launch_depth(const RgKernelArgs *a, hipStream_t stream, size_t
 // plain (nullable): whether the launch runs a PLAIN light instantiation (rg_render_launch.h rg_light_plain)
 static hipError_t dispatch_depth(const RgKernelArgs *a, int maxd, hipStream_t stream, size_t *gt, int *plain = nullptr) {
     if (plain) *plain = 0;
+    if (a->camera) {  // a camera launch (rg_render_*_camera*.hip): primary rays from the eye, frames in the global buffer
+        if (a->px_mask)
+            return rg_heavy_path(*a) ? launch_heavy<RG_MAXD_CAMERA, false, true>(a, stream, gt)
+                                     : launch_light<RG_MAXD_CAMERA, true>(a, stream, gt, plain);
+        return rg_heavy_path(*a) ? launch_heavy<RG_MAXD_CAMERA, false>(a, stream, gt)
+                                 : launch_light<RG_MAXD_CAMERA>(a, stream, gt, plain);
+    }
     if (a->px_mask)  // a sparse launch (rg_render_*_sparse.hip): a tile list and a pixel mask, frames in the global buffer
         return rg_heavy_path(*a) ? launch_heavy<0, false, true>(a, stream, gt) : launch_light<0, true>(a, stream, gt, plain);
     if (host_frame_launch(a)) {

@@ -86,6 +86,16 @@ RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx
     a.inv_w = 1.0 / a.width_d;
     a.inv_h = 1.0 / a.height_d;
     a.plain_veto = (cx->rdiv_ok && s->exact_div) ? 0u : 1u;
+    if (s->has_camera) {  // by value: this launch keeps its camera whatever the scene is given next
+        a.camera = 1u;
+        for (int k = 0; k < 3; ++k) {
+            a.cam_eye[k] = s->camera.eye[k];
+            a.cam_right[k] = s->camera.right[k];
+            a.cam_up[k] = s->camera.up[k];
+            a.cam_forward[k] = s->camera.forward[k];
+        }
+        a.plain_veto |= 4u;  // the PLAIN kernels' camera ray is the reference's view
+    }
     a.rgba = reinterpret_cast<uint32_t *>(d.rgba);
     a.rgb = d.rgb;
     a.tile_flags = d.tile_flags;
@@ -182,9 +192,17 @@ rg_status refresh_prim_table(rg_launch_ctx *cx, RgKernelArgs &a, hipStream_t st)
 rg_status order_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx *cx, RgKernelArgs &a) {
     if (!(s->tile_order == 1 || (s->tile_order < 0 && rg_heavy_path(a)))) return RG_OK;
     const size_t ntiles = (size_t)rg_tile_count(a);
-    const rg_launch_ctx::PermKey key{d.width, d.height, d.tiling.tile_rows, d.tiling.tile_stride,
-                                     d.tiling.tile_offset, d.tile_first, a.out_rows, d.tile_wlog, s->max_depth,
-                                     (uint32_t)s->n_lights, d.tile_group, a.fov_adjustment, s->mats};
+    rg_launch_ctx::PermKey key{d.width, d.height, d.tiling.tile_rows, d.tiling.tile_stride,
+                               d.tiling.tile_offset, d.tile_first, a.out_rows, d.tile_wlog, s->max_depth,
+                               (uint32_t)s->n_lights, d.tile_group, a.fov_adjustment, s->mats};
+    // the probe's rays are the launch's: an order made through one camera is not another's (nor the fixed view's)
+    key.camera = a.camera != 0;
+    for (int k = 0; key.camera && k < 3; ++k) {
+        key.cam[k] = a.cam_eye[k];
+        key.cam[3 + k] = a.cam_right[k];
+        key.cam[6 + k] = a.cam_up[k];
+        key.cam[9 + k] = a.cam_forward[k];
+    }
     const bool cached = cx->perm_valid && cx->perm_key == key;
     // the pair under one capacity (in tiles); a failure here leaves the runtime's last error as it is
     if (!cached && rg_grow(RG_MEM_DEVICE, cx->tile_cap, ntiles,
@@ -320,7 +338,8 @@ rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_
     // host-frame features (rg_render_kernel.h HF) up to rg_host_array_frames() frames;
     // the others the MAXD == 0 kernels, whose frames live in a global buffer
     const bool host_arrays = frames <= rg_host_array_frames() && rg_heavy_path(a);
-    // (so do sparse launches: the SPARSE instantiations exist for MAXD == 0 only)
+    // (so do sparse launches: the SPARSE instantiations exist for MAXD == 0 only; camera launches
+    // keep their frames there whatever `disp` says: rg_launch_global_frames)
     const int disp = ((d.host_frame && !host_arrays) || d.px_mask) ? std::max(frames, rg_max_array_frames() + 1) : frames;
     if ((st = size_deep_frames(cx, a, frames, disp)) != RG_OK) return st;
     if ((st = refresh_prim_table(cx, a, d.stream)) != RG_OK) return st;

@@ -1,4 +1,4 @@
-// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip, rg_resolve.hip and rg_edge.hip
+// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip, rg_tile_order_camera.hip, rg_resolve.hip and rg_edge.hip
 // define for the host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  The defining files
 // include this header too, so the compiler checks every signature against it.
 #pragma once
@@ -14,6 +14,9 @@ extern "C" int rg_max_array_frames(void);
 extern "C" int rg_launch_global_frames(const RgKernelArgs *a, int maxd);
 extern "C" hipError_t rg_launch_tile_order(const RgKernelArgs *a, uint32_t *scratch, uint32_t *perm, hipStream_t stream);
 extern "C" size_t rg_tile_order_scratch_words(uint32_t ntiles);
+// rg_tile_order_camera.hip: rg_launch_tile_order's probe for a launch with a camera (a->camera != 0)
+extern "C" hipError_t rg_launch_tile_probe_camera(const RgKernelArgs *a, uint32_t *bucket_of, uint32_t ntiles,
+                                                  hipStream_t stream);
 // rg_resolve.hip: rows x width output pixels from (k rows) x (k width) packed f32 RGB samples
 // (device memory; rgb nullable); hipErrorInvalidValue for k outside 1..8.
 extern "C" hipError_t rg_launch_resolve(const float *in, uint32_t width, uint32_t rows, uint32_t k, uint8_t *rgba,

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/raingun.h"
+#include "rg_camera.h"
 #include "rg_device.h"
 #include "rg_k_bvh.h"
 #include "rg_k_diag.h"
@@ -87,7 +88,9 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
 // that a.nan_scene is 0 and that a.n_lights == LB, so the kernel holds them as compile-time facts.
 // It has also checked what lets a PLAIN kernel replace divisions by launch constants with exact forms
 // (rg_exact.h): the camera quotients of this frame size, the camera ray's range, the blob image.
-// SPARSE (MAXD == 0 only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
+// MAXD == RG_MAXD_CAMERA (the camera family): the MAXD == 0 kernel whose primary rays leave
+// a.cam_eye in the directions of rg_camera.h and are traced by the general closest-hit query.
+// SPARSE (global frames only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
 // renders its pixel only where a.px_mask says so (adaptive anti-aliasing, rg_aa.hip; RgKernelArgs::px_mask).
 template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
           bool HF = false, bool SPARSE = false, bool PLAIN = false>
@@ -266,7 +269,7 @@ void rg_render_kernel(RgKernelArgs a) {
         nring = 0;
     };
     uint32_t n_prim = 0, n_shadow = 0, n_sec = 0;
-    FrameStack<MAXD> stk;  // K::global_frames (MAXD 0): field-major frames in a global buffer, no scratch array
+    FrameStack<K::array_frames> stk;  // K::global_frames: field-major frames in a global buffer, no scratch array
     stk.init(a);
 
     // Sharded tile queue: RG_NQ heads, head q serving tiles q, q + RG_NQ, ... (one
@@ -824,16 +827,28 @@ void rg_render_kernel(RgKernelArgs a) {
                     } else {
                         sensor_div(a, x, y, sx, sy);
                     }
+                    if constexpr (K::camera) {
+                        // the launch's camera (rg_camera.h): a ray from its eye, which the loop below
+                        // traces as the general closest-hit query at depth 0 that it is -- nothing of
+                        // trace_primary's o = 0 (sph_cc, the planes' o.n, the camera buffer) holds for it
+                        double dir[3];
+                        rg_camera_direction(a.cam_right, a.cam_up, a.cam_forward, sx, sy, dir);
+                        q.o = v3(a.cam_eye[0], a.cam_eye[1], a.cam_eye[2]);
+                        q.d = v3(dir[0], dir[1], dir[2]);
+                        n_prim++;
+                        have_result = false;
+                    } else {
                     q.o = v3(0.0, 0.0, 0.0);
                     if constexpr (fast_camera) q.d = normalize_camera(sx, sy);
                     else q.d = normalize(v3(sx, sy, -1.0));
                     n_prim++;
                     closest_init(c);
                     trace_primary<F32F, BVH, PLAIN>(a, src, q.d, c);
+                    have_result = true;
+                    }
                     mode = MODE_CLOSEST;
                     qdepth = 0;
                     task = -1;
-                    have_result = true;
                 }
                 continue;
             }
@@ -943,7 +958,9 @@ void rg_render_kernel(RgKernelArgs a) {
                 r1.o = q.o;
                 const bool shadow = mode == MODE_SHADOW || mode == MODE_SHADOW_H;
                 r1.d = shadow ? sb.d[0] : q.d;
-                const bool lane_walk = (shadow ? hdepth : qdepth) >= (int)a.lane_min_depth;
+                // (a camera ray walks with its wave, as the primary ray it is, whatever lane_min_depth says)
+                const bool lane_walk = (shadow ? hdepth : qdepth) >= (int)a.lane_min_depth &&
+                                       !(K::camera && !shadow && qdepth == 0);
                 // a shadow ray that could see a NaN distance (ray_exotic) runs as a
                 // fully counted closest-hit query: in_light = none || dist > light
                 // distance (rendering.rs:150-155), the scene.rs:38 panic iff >= 2 hits, one NaN

@@ -2,7 +2,8 @@
 // runs -- launch_light / launch_heavy choose the kernel, launch_waves what it stages in LDS -- and
 // launch_one, which asks the occupancy, takes the grid from rg_render_grid.h and launches.
 // launch_light<MAXD, SPARSE> / launch_heavy<MAXD, HF, SPARSE> are instantiated explicitly, one per
-// rg_render_*.hip (SPARSE: the launches of a tile list under a pixel mask, MAXD == 0 only), so every
+// rg_render_*.hip (SPARSE: the launches of a tile list under a pixel mask, global frames only;
+// MAXD = RG_MAXD_CAMERA: the launches of a scene with a camera), so every
 // rg_render_kernel instantiation is emitted by exactly one translation unit (the occupancy cache
 // and the HIP runtime identify a kernel by its host address); the dispatcher (rg_kernels.hip
 // dispatch_depth) sees only the declarations below.
@@ -158,7 +159,7 @@ static hipError_t launch_light_one(const RgKernelArgs *a, hipStream_t stream, si
 template <int MAXD, bool SPARSE = false>
 __attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs *a, hipStream_t stream, size_t *gt,
                                                               int *ran_plain) {
-    const bool plain = MAXD != 0 && !SPARSE && rg_light_plain(*a);
+    const bool plain = MAXD > 0 && !SPARSE && rg_light_plain(*a);
     if (ran_plain) *ran_plain = plain ? 1 : 0;
     return rg_light_ladder(a->n_lights, [&](auto step) -> hipError_t {
         using S = decltype(step);
@@ -169,7 +170,7 @@ __attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs
             // occupancy balance the tiles dynamically, where a fixed tiles-per-wave grid makes every
             // wave render exactly that many tiles and the slowest wave's sum the makespan
             // (2: launches below RG_LIGHT_BIG_TILES tiles only -- rg_render_multi's shares and bands)
-            if constexpr (MAXD != 0 && RG_LIGHT_SINGLE_PERSISTENT != 0) {
+            if constexpr (MAXD > 0 && RG_LIGHT_SINGLE_PERSISTENT != 0) {
                 if (!a->pipelined && (RG_LIGHT_SINGLE_PERSISTENT != 2 || rg_tile_count(*a) < RG_LIGHT_BIG_TILES))
                     return launch_light_one<LightCfg<MAXD, S::wps, S::lights, RG_TPW_PERSISTENT>>(a, stream, gt, plain);
             }
@@ -177,7 +178,7 @@ __attribute__((visibility("hidden"))) hipError_t launch_light(const RgKernelArgs
             // whole frames (frames in flight): RG_LIGHT_TPW_BIG tiles per wave, half the waves of
             // RG_LIGHT_TILES_PER_WAVE (as a compile-time variant: test1 0.2968 -> 0.2943 ms over 200
             // frames, profiles/r06/s43); smaller launches (the 1/N shares) keep 16
-            if constexpr (MAXD != 0 && S::lights == RG_LB) {
+            if constexpr (MAXD > 0 && S::lights == RG_LB) {
                 if (rg_tile_count(*a) >= RG_LIGHT_BIG_TILES)
                     return launch_light_one<LightCfg<MAXD, S::wps, S::lights, RG_LIGHT_TPW_BIG>>(a, stream, gt, plain);
             }
@@ -226,3 +227,8 @@ extern template hipError_t launch_heavy<0, false>(const RgKernelArgs *, hipStrea
 extern template hipError_t launch_heavy<8, true>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_light<0, true>(const RgKernelArgs *, hipStream_t, size_t *, int *);
 extern template hipError_t launch_heavy<0, false, true>(const RgKernelArgs *, hipStream_t, size_t *);
+// the camera family (rg_render_*_camera*.hip): dense and sparse, light and heavy
+extern template hipError_t launch_light<RG_MAXD_CAMERA>(const RgKernelArgs *, hipStream_t, size_t *, int *);
+extern template hipError_t launch_heavy<RG_MAXD_CAMERA, false>(const RgKernelArgs *, hipStream_t, size_t *);
+extern template hipError_t launch_light<RG_MAXD_CAMERA, true>(const RgKernelArgs *, hipStream_t, size_t *, int *);
+extern template hipError_t launch_heavy<RG_MAXD_CAMERA, false, true>(const RgKernelArgs *, hipStream_t, size_t *);

@@ -15,6 +15,7 @@
 #include "../../include/raingun.h"
 #include "../../include/raingun_debug.h"
 #include "rg_bvh.h"
+#include "rg_camera.h"
 #include "rg_device.h"
 #include "rg_exact.h"
 #include "rg_lightbuf.h"
@@ -332,6 +333,8 @@ void rg_sync_settings(rg_scene *dst, const rg_scene *src) {
     dst->bvh_enabled = src->bvh_enabled;
     dst->lbuf_enabled = src->lbuf_enabled;
     dst->exact_div = src->exact_div;
+    dst->has_camera = src->has_camera;
+    dst->camera = src->camera;
     dst->lane_min_depth = src->lane_min_depth;
     dst->tile_order = src->tile_order;
     dst->ring_flush_small = src->ring_flush_small;
@@ -564,6 +567,27 @@ void rg_scene_destroy(rg_scene *s) { release(s); }
 rg_status rg_scene_set_max_depth(rg_scene *s, uint32_t max_depth) {
     if (!s) return RG_ERR_INVALID_ARGUMENT;
     s->max_depth = max_depth;
+    return RG_OK;
+}
+
+rg_status rg_camera_look_at(const double eye[3], const double target[3], const double up[3], rg_camera *out) {
+    if (!eye || !target || !up || !out) return RG_ERR_INVALID_ARGUMENT;
+    rg_camera c;
+    if (!rg_camera_look_at_basis(eye, target, up, c.right, c.up, c.forward)) return RG_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < 3; ++k) c.eye[k] = eye[k];
+    *out = c;
+    return RG_OK;
+}
+
+rg_status rg_scene_set_camera(rg_scene *s, const rg_camera *camera) {
+    if (!s) return RG_ERR_INVALID_ARGUMENT;
+    if (!camera) {  // the reference's view again: the launches and kernels of a scene that never had a camera
+        s->has_camera = false;
+        return RG_OK;
+    }
+    if (!rg_camera_valid(camera->eye, camera->right, camera->up, camera->forward)) return RG_ERR_INVALID_ARGUMENT;
+    s->camera = *camera;
+    s->has_camera = true;
     return RG_OK;
 }
 

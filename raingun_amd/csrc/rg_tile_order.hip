@@ -6,6 +6,7 @@
 #include "rg_k_frames.h"
 #include "rg_k_trace.h"
 #include "rg_launchers.h"
+#include "rg_tile_probe.h"
 
 #pragma clang fp contract(off)
 
@@ -21,22 +22,7 @@ using namespace rgk;
 // tile queue by descending weight (longest-processing-time-first).  This changes only the
 // order in which tiles are dequeued: every pixel is still computed once, by
 // the same code, so the output is identical.
-#define RG_PROBE_SAMPLES 8   // per tile: 4 corners + 4 inner points; 8 tiles per wave
-#define RG_ORDER_BUCKETS 16
-
-__device__ __forceinline__ uint32_t probe_weight(const RgKernelArgs &a, const Closest &c) {
-    if (c.id < 0) return 1u;                                        // sky: one ray
-    const int s = a.mats[c.id].surface;
-    const uint32_t diffuse = 2u + (uint32_t)a.n_lights;              // primary + shadow rays
-    if (a.max_depth <= 1) return diffuse;
-    if (s == RG_SURFACE_REFRACTIVE) return 8u * diffuse;            // a ray tree below the hit
-    if (s == RG_SURFACE_REFLECTING) return 3u * diffuse;            // a reflection chain
-    return diffuse;
-}
-// bucket 0 = heaviest; a tile's weight is the sum of its 8 samples
-__device__ __forceinline__ uint32_t order_bucket(uint32_t w) {
-    return (RG_ORDER_BUCKETS - 1u) - min(w >> 4, RG_ORDER_BUCKETS - 1u);
-}
+// (RG_PROBE_SAMPLES, probe_weight and order_bucket: rg_tile_probe.h, shared with the camera probe)
 
 #define RG_ORDER_CHUNK 1024  // tiles per counting/scatter chunk (one wave each)
 
@@ -155,7 +141,10 @@ extern "C" hipError_t rg_launch_tile_order(const RgKernelArgs *a, uint32_t *scra
     const uint32_t nchunks = (ntiles + RG_ORDER_CHUNK - 1u) / RG_ORDER_CHUNK;
     uint32_t *bucket_of = scratch, *chunk_hist = scratch + ntiles;
     const uint32_t lanes = ntiles * RG_PROBE_SAMPLES;
-    if (a->n_nodes > 0)
+    if (a->camera) {  // the camera's rays (rg_tile_order_camera.hip)
+        const hipError_t e = rg_launch_tile_probe_camera(a, bucket_of, ntiles, stream);
+        if (e != hipSuccess) return e;
+    } else if (a->n_nodes > 0)
         hipLaunchKernelGGL(rg_tile_probe_kernel<true>, dim3((lanes + 255u) / 256u), dim3(256), 0, stream, *a, bucket_of,
                            ntiles);
     else

@@ -2,8 +2,12 @@
 // on the native host layer (libraingun_host.so: YAML scene, textures, PNG) and
 // the HIP renderer (libraingun_hip.so: rg_render_image).
 //
-//   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T] [-o FILE] [--gpu N] FILE
+//   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
+//           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [-o FILE] [--gpu N] FILE
 //
+// --eye / --look-at / --up (not in the reference, whose view is from the origin down -z): the camera
+// (rg_camera_look_at, rg_scene_set_camera).  --up defaults to 0,1,0; --eye without --look-at looks down
+// -z from the eye; a malformed triple or a rejected look-at is an argument error.  No camera key in the YAML.
 // --adaptive T (0..256; not in the reference): the N x N rays only for pixels whose 8-neighbourhood
 // contrast in the 1-sample frame is at least T (rg_render_image_aa_adaptive); accepted with
 // --samples 1, where it has no effect.
@@ -43,6 +47,9 @@ const char *kHelp =
     "        --preview    Shows render progress in a window (not available: renders without one).\n"
     "    -V, --version    Prints version information\n\n"
     "OPTIONS:\n"
+    "        --eye <X,Y,Z>          Camera position (default 0,0,0).\n"
+    "        --look-at <X,Y,Z>      Point the camera looks at (default: straight down -z from the eye).\n"
+    "        --up <X,Y,Z>           Up hint of --look-at (default 0,1,0).\n"
     "        --adaptive <T>         Adaptive anti-aliasing: the N x N rays only where the 1-sample frame's contrast is at least T (0..256).\n"
     "        --gpu <N>              HIP device to render on (default 0).\n"
     "    -h, --height <PIXELS>      Height of output image.\n"
@@ -66,7 +73,7 @@ const char *kHelp =
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
     const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr,
-               *adaptive = nullptr;
+               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr;
     int gpu = 0;
 };
 
@@ -77,7 +84,22 @@ struct RenderOptions {  // render.rs:32-46
     uint32_t adaptive = 0;  // contrast threshold (--adaptive)
     bool has_depth = false;
     uint32_t max_recursion_depth = 0;
+    bool has_camera = false;  // --eye / --look-at / --up
+    rg_camera camera{};
 };
+
+bool parse_triple(const char *s, double out[3]) {  // "X,Y,Z": three finite numbers, nothing else
+    if (!s) return false;
+    for (int k = 0; k < 3; ++k) {
+        if (!*s || *s == ' ' || *s == '\t') return false;  // (strtod would skip the blank)
+        char *end = nullptr;
+        out[k] = std::strtod(s, &end);
+        if (end == s || !(out[k] - out[k] == 0.0)) return false;
+        if (*end != (k < 2 ? ',' : '\0')) return false;
+        s = end + 1;
+    }
+    return true;
+}
 
 bool parse_u32(const char *s, uint32_t *out) {  // str::parse::<u32>
     if (!s || !*s) return false;
@@ -121,6 +143,9 @@ Args parse_args(int argc, char **argv) {
             else if (name == "gpu") a.gpu = std::atoi(take_value(i, "--gpu <N>", val));
             else if (name == "samples") a.samples = take_value(i, "--samples <N>", val);
             else if (name == "adaptive") a.adaptive = take_value(i, "--adaptive <T>", val);
+            else if (name == "eye") a.eye = take_value(i, "--eye <X,Y,Z>", val);
+            else if (name == "look-at") a.look_at = take_value(i, "--look-at <X,Y,Z>", val);
+            else if (name == "up") a.up = take_value(i, "--up <X,Y,Z>", val);
             else if (val) clap_error("Found argument '" + std::string(arg) + "' which wasn't expected, or isn't valid in this context");
             else if (name == "4k") { a.uhd = true; a.hd = false; }   // overrides_with("hd")
             else if (name == "hd") { a.hd = true; a.uhd = false; }   // overrides_with("4k")
@@ -156,6 +181,22 @@ RenderOptions options_from(const Args &a) {  // main.rs:70-96
         if (o.adaptive > 256)
             clap_error(std::string("Invalid value for '--adaptive <T>': ") + a.adaptive + " is not between 0 and 256");
         o.has_adaptive = true;
+    }
+    if (a.up && !a.look_at) clap_error("The argument '--up <X,Y,Z>' needs '--look-at <X,Y,Z>'");
+    if (a.eye || a.look_at) {
+        double eye[3] = {0.0, 0.0, 0.0}, target[3], up[3] = {0.0, 1.0, 0.0};
+        if (a.eye && !parse_triple(a.eye, eye)) clap_error(std::string("Invalid value for '--eye <X,Y,Z>': ") + a.eye);
+        if (a.look_at && !parse_triple(a.look_at, target))
+            clap_error(std::string("Invalid value for '--look-at <X,Y,Z>': ") + a.look_at);
+        if (a.up && !parse_triple(a.up, up)) clap_error(std::string("Invalid value for '--up <X,Y,Z>': ") + a.up);
+        if (a.look_at) {
+            if (rg_camera_look_at(eye, target, up, &o.camera) != RG_OK)
+                clap_error("Invalid camera: --look-at equals --eye, or --up is parallel to the view direction");
+        } else {  // straight down -z from the eye
+            const rg_camera c = {{eye[0], eye[1], eye[2]}, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, -1.0}};
+            o.camera = c;
+        }
+        o.has_camera = true;
     }
     if (a.draft) {
         o.has_depth = true;
@@ -220,6 +261,8 @@ int main(int argc, char **argv) {
     rg_scene *scene = nullptr;
     st = rg_scene_create(rgh_scene_desc(loaded), args.gpu, &scene);
     if (st != RG_OK) panic(std::string("rg_scene_create: ") + rg_status_string(st));
+    if (opts.has_camera && (st = rg_scene_set_camera(scene, &opts.camera)) != RG_OK)
+        panic(std::string("rg_scene_set_camera: ") + rg_status_string(st));
     std::vector<uint8_t> rgba((size_t)opts.width * opts.height * 4);
 
     auto t0 = std::chrono::steady_clock::now();  // render.rs:54-56

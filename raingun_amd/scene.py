@@ -27,6 +27,7 @@ from typing import Callable, List, Optional, Sequence, Union
 import numpy as np
 
 from . import _abi
+from .camera import Camera
 from .color import Color
 
 
@@ -341,6 +342,17 @@ class DeviceScene:
     def set_max_depth(self, depth: int) -> None:
         _abi.check(_abi.lib().rg_scene_set_max_depth(self.handle, int(depth)))
 
+    def set_camera(self, camera: Optional[Camera]) -> None:
+        """rg_scene_set_camera: the camera of every later render of this scene (raingun_amd/camera.py);
+        None restores the reference's view from the origin down -z.  Launches already enqueued keep
+        the camera they were enqueued with."""
+        if camera is None:
+            _abi.check(_abi.lib().rg_scene_set_camera(self.handle, None), "rg_scene_set_camera")
+            return
+        c = _abi.rg_camera((C.c_double * 3)(*camera.eye), (C.c_double * 3)(*camera.right),
+                           (C.c_double * 3)(*camera.up), (C.c_double * 3)(*camera.forward))
+        _abi.check(_abi.lib().rg_scene_set_camera(self.handle, C.byref(c)), "rg_scene_set_camera")
+
     def render_image(self, width: int, height: int, stats: Optional[_abi.rg_stats] = None,
                      out: Optional[np.ndarray] = None) -> np.ndarray:
         """rendering::render_image (rendering.rs:24-38) into host memory.  `out`
@@ -494,9 +506,10 @@ class Scene:                   # scene.rs:11-31
     # samples > 1: samples x samples rays per pixel, box-filtered (rg_render_image_aa);
     # adaptive = T (0..256): only for pixels on edges of the 1-sample frame (rg_render_image_aa_adaptive)
     def render_image(self, width: int, height: int, device: int = 0, samples: int = 1,
-                     adaptive: Optional[int] = None) -> np.ndarray:
+                     adaptive: Optional[int] = None, camera: Optional[Camera] = None) -> np.ndarray:
         ds = DeviceScene(self, device)
         try:
+            ds.set_camera(camera)
             if adaptive is not None:
                 return ds.render_image_aa_adaptive(width, height, samples, adaptive)
             if samples != 1:
@@ -510,10 +523,11 @@ class Scene:                   # scene.rs:11-31
     # bands of `tile_rows` finished RGBA8 rows.  Return True from it to cancel.
     def streaming_render(self, width: int, height: int,
                          on_tile: Callable[[int, np.ndarray], Optional[bool]],
-                         tile_rows: int = 16, device: int = 0) -> _abi.rg_stats:
+                         tile_rows: int = 16, device: int = 0, camera: Optional[Camera] = None) -> _abi.rg_stats:
         ds = DeviceScene(self, device)
         stats = _abi.rg_stats()
         try:
+            ds.set_camera(camera)
             _abi.check(ds.render_stream(width, height, on_tile, tile_rows, stats), "rg_render_stream")
         finally:
             ds.close()

@@ -4,13 +4,17 @@ compiler remarks, assembly and profiles: scripts/resources.py, scripts/isa_budge
 
     parse(name)    -> {"MAXD": 8, "LSPH": True, ...}, or None if name is no rg_render_kernel
     mangle(**p)    -> the name
-    describe(p)    -> "light", "heavy host", "light tpw=-1 plain", ...
+    describe(p)    -> "light", "heavy host", "light tpw=-1 plain", "heavy camera sparse", ...
+
+MAXD: array frames per lane; 0: frames in the global buffer; MAXD_CAMERA (-1, mangled Lin1E): the same
+with the primary rays of a movable camera (the camera family).
 """
 import re
 
 # (name, is_int) in the template's order
 PARAMS = [("MAXD", True), ("LSPH", False), ("LCOLD", False), ("WPS", True), ("LBT", True), ("F32F", False),
           ("BVH", False), ("TASKS", False), ("TPW", True), ("HF", False), ("SPARSE", False), ("PLAIN", False)]
+MAXD_CAMERA = -1
 _ARG = {True: r"Li(n?\d+)E", False: r"Lb([01])E"}
 _NAME = re.compile("^_Z16rg_render_kernelI" + "".join(_ARG[i] for _, i in PARAMS) + "Ev12RgKernelArgs$")
 
@@ -35,6 +39,8 @@ def describe(p):
         kind += f" tpw={p['TPW']}"
     if p["HF"]:
         kind += " host"
+    if p["MAXD"] == MAXD_CAMERA:
+        kind += " camera"
     if p["SPARSE"]:
         kind += " sparse"
     if p["PLAIN"]:

@@ -1,11 +1,13 @@
 """Per-instantiation register/scratch summary of rg_render_kernel.
 
-    python scripts/resources.py [extra hipcc flags...]
+    python scripts/resources.py [--camera] [extra hipcc flags...]
 
 Compiles the three depth-8 files (rg_render_heavy_d8_host.hip, rg_render_light_d8.hip,
 rg_render_heavy_d8.hip) with the library's flags and -Rpass-analysis=kernel-resource-usage and prints VGPRs, spilled VGPRs, scratch bytes per lane, occupancy and static LDS for the
 MAXD = 8 instantiations (the ones the bench configurations run; "host": the
-host-frame ones, "tpw=-1": the light path's persistent single launches)."""
+host-frame ones, "tpw=-1": the light path's persistent single launches).
+--camera: instead, the camera family (MAXD = -1: rg_render_{light,heavy}_camera{,_sparse}.hip) beside
+the MAXD = 0 kernels it derives from (rg_render_{light,heavy}_{d0,sparse}.hip), MAXD printed first."""
 import re
 import subprocess
 import sys
@@ -15,6 +17,12 @@ from render_kernel_name import describe, parse
 
 CSRC = Path(__file__).resolve().parent.parent / "raingun_amd" / "csrc"
 UNITS = ["rg_render_heavy_d8_host", "rg_render_light_d8", "rg_render_heavy_d8"]
+SHOW = (8,)
+if "--camera" in sys.argv[1:]:
+    sys.argv.remove("--camera")
+    UNITS = ["rg_render_light_d0", "rg_render_light_camera", "rg_render_light_sparse", "rg_render_light_camera_sparse",
+             "rg_render_heavy_d0", "rg_render_heavy_camera", "rg_render_heavy_sparse", "rg_render_heavy_camera_sparse"]
+    SHOW = (0, -1)
 procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
                            "-fno-fast-math", "-fPIC", "-c", u + ".hip", "-o", f"/tmp/{u}_res.o",
                            "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:]],
@@ -37,7 +45,7 @@ for line in remarks:
         cur[m.group(1)] = int(m.group(2))
 for r in rows:
     k = parse(r["name"])
-    if k is None or k["MAXD"] != 8:
+    if k is None or k["MAXD"] not in SHOW:
         continue
     args = ",".join(str(int(k[n])) for n in ("MAXD", "LSPH", "LCOLD", "WPS", "LBT", "F32F", "BVH", "TASKS"))
     print(f"{describe(k):18s} <{args}>  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}"
