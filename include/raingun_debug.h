@@ -161,6 +161,19 @@ rg_status rg_debug_set_exact_div(rg_scene *scene, int32_t enable);
 rg_status rg_debug_camera_check(const rg_scene *scene, uint32_t width, uint32_t height, double fov,
                                 uint64_t *mismatches, int32_t *admitted);
 
+/* The PLAIN light kernels take ONE f64 square root and reciprocal -- a spherical light's distance
+ * and 1 / distance at every shaded hit -- without the range scaling around them, in every lane whose
+ * operand's exponent lies in a window around 1 (biased exponent 767..1279); the other lanes of such a
+ * wave take the compiler's own sqrt and division.  Every other sqrt and division of those kernels is
+ * the compiler's.  rg_debug_unscaled_check runs the guarded primitives on the device for n
+ * caller-supplied operands (n <= 2^24) --
+ * op 3: sqrt(a[i]) and 1.0 / sqrt(a[i]) from one admission, the form the kernels run;
+ * op 0: sqrt(a[i]); 1: 1.0 / a[i]; 2: a[i] / b[i] (b is read by op 2 only): the same scheme for a
+ * lone root, reciprocal and quotient, which no render kernel runs (they measured slower there) --
+ * and beside them the compiler's operations; *mismatches = the operands whose results differ in any bit. */
+rg_status rg_debug_unscaled_check(const rg_scene *scene, int32_t op, const double *a, const double *b, uint32_t n,
+                                  uint64_t *mismatches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,7 +158,7 @@ DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "
                  "rg_debug_fail_split_a", "rg_debug_set_host_ring", "rg_debug_set_host_tile_shape", "rg_debug_set_multi", "rg_debug_gather_noop",
                  "rg_debug_counter_words", "rg_debug_set_aa_band_rows",
                  "rg_debug_set_aa_adaptive_timing", "rg_debug_aa_adaptive_info", "rg_debug_last_plain",
-                 "rg_debug_set_exact_div", "rg_debug_camera_check")
+                 "rg_debug_set_exact_div", "rg_debug_camera_check", "rg_debug_unscaled_check")
 # include/raingun_frames.h
 FRAMES_SYMBOLS = ("rg_frames_create", "rg_frames_destroy", "rg_frames_step", "rg_frames_flush", "rg_frames_image",
                   "rg_frames_read_image", "rg_frames_status", "rg_frames_set_batch", "rg_frames_set_root_tiles", "rg_comm_id_bytes",
@@ -256,6 +256,9 @@ def _declare(lib: C.CDLL) -> None:
         lib.rg_debug_set_exact_div.argtypes = [C.c_void_p, C.c_int32]
         lib.rg_debug_camera_check.restype = C.c_int32
         lib.rg_debug_camera_check.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, P(C.c_uint64), P(C.c_int32)]
+    if hasattr(lib, "rg_debug_unscaled_check"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
+        lib.rg_debug_unscaled_check.restype = C.c_int32
+        lib.rg_debug_unscaled_check.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint64)]
     lib.rg_frames_create.restype = C.c_int32
     lib.rg_frames_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p, P(C.c_void_p)]

@@ -582,6 +582,31 @@ rg_status rg_debug_camera_check(const rg_scene *s, uint32_t width, uint32_t heig
     return st;
 }
 
+rg_status rg_debug_unscaled_check(const rg_scene *s, int32_t op, const double *a, const double *b, uint32_t n,
+                                  uint64_t *mismatches) {
+    if (!s || !a || !mismatches || n == 0 || n > (1u << 24) || op < 0 || op > 3 || (op == 2 && !b))
+        return RG_ERR_INVALID_ARGUMENT;
+    if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
+    const size_t bytes = (size_t)n * sizeof(double);
+    double *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
+    unsigned long long *d_bad = nullptr, bad = 0;
+    rg_status st = RG_OK;
+    if (!ok(hipMalloc(&d_a, bytes)) || (op == 2 && !ok(hipMalloc(&d_b, bytes))) || !ok(hipMalloc(&d_out, 2 * bytes)) ||
+        !ok(hipMalloc(&d_bad, sizeof bad)))
+        st = RG_ERR_OUT_OF_MEMORY;
+    else if (!ok(hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice)) ||
+             (op == 2 && !ok(hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice))) || !ok(hipMemset(d_out, 0, 2 * bytes)) ||
+             !ok(hipMemset(d_bad, 0, sizeof bad)) || !ok(rg_launch_unscaled_check(op, d_a, d_b, n, d_out, d_bad, nullptr)) ||
+             !ok(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost)))
+        st = RG_ERR_DEVICE;
+    (void)hipFree(d_a);
+    (void)hipFree(d_b);
+    (void)hipFree(d_out);
+    (void)hipFree(d_bad);
+    *mismatches = bad;
+    return st;
+}
+
 rg_status rg_debug_counter_words(const rg_scene *s, int32_t first, int32_t n, uint64_t *out) {
     if (!s || !out || first < 0 || n < 0 || first + n > RG_COUNTER_WORDS) return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;

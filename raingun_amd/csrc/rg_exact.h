@@ -9,6 +9,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #if defined(__HIP__) || defined(__HIPCC__)
 #define RG_EXACT_FN __host__ __device__ inline
@@ -103,6 +104,42 @@ inline void rg_plane_axes(const double n[3], double xa[3], double ya[3]) {
 // value, and the expansions without them (rg_k_math.h sqrt_unscaled / rcp_unscaled) give the same
 // bits.  2^100 is no limit of the method, just far more than a camera needs (fov 179.9 degrees at
 // an aspect of 4096 : 1 gives s ~ 2^44) and far less than the thresholds.  A NaN fails the test.
+//
+// The same expansions without their scaling, for operands only the LANE knows (rg_k_math.h
+// sqrt_guarded / rcp_guarded / div_guarded): the admission is a test of the operand's exponent field.
+// What the instructions and hipcc's expansions do outside the plain path, by their documentation:
+//   * sqrt: ldexp(x, 256) in front and ldexp(., -128) behind where x < 2^-767; x itself for 0 and +inf
+//     (v_cmp_class); a negative operand or a NaN goes through v_rsq_f64 to NaN;
+//   * v_div_scale_f64 scales (by 2^+-128) where the denominator is denormal or its reciprocal would be
+//     (biased exponent 0 or >= 2045), where the numerator's exponent is <= 53, where exponent(num) -
+//     exponent(den) >= 768, or where the quotient would be denormal (difference <= -1023); v_div_fmas_f64
+//     applies the scale only where v_div_scale said so; v_div_fixup_f64 replaces the value for a NaN,
+//     zero or infinite operand and for quotients under- or overflowing, else copies it with the sign of
+//     num ^ den, which the fma chain's nonzero result has already.
+// With every operand's biased exponent in [RG_UNSCALED_EXP_LO, RG_UNSCALED_EXP_HI] = [767, 1279] (1023
+// +- 256: |x| in [2^-256, 2^257)) none of that applies: x >= 2^-256 > 2^-767; exponents are > 53 and
+// < 2045; two of them differ by at most 512 < 768, so a quotient lies in (2^-513, 2^514): normal; every
+// intermediate of the refinement (the reciprocal, residuals of relative size >= 2^-108 or exactly 0) is
+// normal or zero.  sqrt of an admitted x has its exponent in [-128, 128]: admitted as a divisor, so one
+// test covers 1.0 / sqrt(x).  +-256 binades are no limit of the method (the nearest threshold, the
+// numerator's exponent <= 53, is 714 binades below the window): they cover what a scene with
+// coordinates below 1e100 that is worth the fast path produces, in one unsigned compare on the high
+// dword -- which 0, denormals, inf, NaN, the far ends and (for sqrt, where the sign bit is part of
+// the compared field) negative operands all fail.
+#define RG_UNSCALED_EXP_LO 767u
+#define RG_UNSCALED_EXP_HI 1279u
+// hi: the operand's high dword.  sqrt's admission: a set sign bit fails.
+RG_EXACT_FN bool rg_unscaled_ok_hi(uint32_t hi) {
+    return hi - (RG_UNSCALED_EXP_LO << 20) < ((RG_UNSCALED_EXP_HI - RG_UNSCALED_EXP_LO + 1u) << 20);
+}
+// a division's operand: either sign
+RG_EXACT_FN bool rg_unscaled_ok_abs_hi(uint32_t hi) { return rg_unscaled_ok_hi(hi & 0x7fffffffu); }
+inline uint32_t rg_high_dword(double x) {
+    uint64_t b;
+    memcpy(&b, &x, sizeof b);
+    return (uint32_t)(b >> 32);
+}
+
 #define RG_CAMERA_S_MAX 1.2676506002282294e30  // 2^100
 inline bool rg_camera_unscaled_ok(double fov_adjustment, double aspect) {
     const double s = 1.0 + (fov_adjustment * fov_adjustment) * (1.0 + aspect * aspect);

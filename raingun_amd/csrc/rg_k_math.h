@@ -56,6 +56,60 @@ __device__ __forceinline__ double rcp_unscaled(double m) {
     return __builtin_fma(__builtin_fma(-m, r, 1.0), r, r);
 }
 
+// The same for operands only the lane knows: the lane is admitted by its operand's
+// exponent field (rg_exact.h rg_unscaled_ok_hi: biased exponent in [767, 1279], where every scaling
+// and fixup of the expansion is the identity), and where any lane of the wave is not, those lanes take
+// the compiler's own sqrt / division under a wave-uniform branch -- so a wave of ordinary operands
+// never executes the expansion, and 0, denormals, inf, NaN, negative sqrt operands and the far ends
+// come out as they always did.  The PLAIN kernels' one use (RG_PLAIN_ULIGHT; 0: as the other kernels,
+// for A/B builds): the spherical lights' direction and distance, sqrt_rcp_guarded in rg_k_shade.h
+// light_dir_dist.  In sphere_tail, the planes' quotients and fresnel / transmission the same
+// primitives measured SLOWER than the compiler's expansions, in the sphere normal no faster, and all
+// were taken out again; sqrt_guarded, rcp_guarded and div_guarded stay only as the forms
+// rg_debug_unscaled_check proves on the device -- no render kernel calls them.
+#ifndef RG_PLAIN_ULIGHT
+#define RG_PLAIN_ULIGHT 1
+#endif
+__device__ __forceinline__ uint32_t high_dword(double x) { return (uint32_t)__double2hiint(x); }
+__device__ __forceinline__ double sqrt_guarded(double x) {
+    const bool ok = rg_unscaled_ok_hi(high_dword(x));
+    double r = sqrt_unscaled(x);
+    if (__any(!ok)) {
+        if (!ok) r = sqrt(x);
+    }
+    return r;
+}
+__device__ __forceinline__ double rcp_guarded(double m) {
+    const bool ok = rg_unscaled_ok_abs_hi(high_dword(m));
+    double r = rcp_unscaled(m);
+    if (__any(!ok)) {
+        if (!ok) r = 1.0 / m;
+    }
+    return r;
+}
+// m = sqrt(x) and 1.0 / m: an admitted x has m in [2^-128, 2^129), admitted as a divisor
+__device__ __forceinline__ void sqrt_rcp_guarded(double x, double &m, double &inv) {
+    const bool ok = rg_unscaled_ok_hi(high_dword(x));
+    m = sqrt_unscaled(x);
+    inv = rcp_unscaled(m);
+    if (__any(!ok)) {
+        if (!ok) { m = sqrt(x); inv = 1.0 / m; }
+    }
+}
+// a / b: the reciprocal's refinement, q = a r, and one residual step on the quotient -- what hipcc
+// emits between v_div_scale_f64 and v_div_fixup_f64, v_div_fmas_f64 without its scale
+__device__ __forceinline__ double div_guarded(double a, double b) {
+    const bool ok = rg_unscaled_ok_abs_hi(high_dword(a)) && rg_unscaled_ok_abs_hi(high_dword(b));
+    double r = __builtin_amdgcn_rcp(b);
+    r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
+    r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
+    double q = a * r;
+    q = __builtin_fma(__builtin_fma(-b, q, a), r, q);
+    if (__any(!ok)) {
+        if (!ok) q = a / b;
+    }
+    return q;
+}
 // The primary ray's sensor coordinates (ray.rs:46-51) of pixel (x, y).  _div: the reference's two
 // divisions.  _recip (PLAIN kernels): the residual-form quotients of rg_exact.h with the host's
 // a.inv_w / a.inv_h, which the launcher admits only after rg_recip_div_ok has compared every

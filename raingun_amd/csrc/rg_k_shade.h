@@ -206,6 +206,9 @@ __device__ __forceinline__ bool transmission(V3 n, V3 inc, V3 h, float index, Ra
 
 // direction_from + distance for one light (lights.rs:46-58).  For a spherical
 // light both use |pos - p| = sqrt(dot(v, v)): computed once, same bits.
+// U (the PLAIN light kernels, RG_PLAIN_ULIGHT): the square root and the reciprocal without their range
+// scaling in the lanes whose operand admits it (rg_k_math.h sqrt_rcp_guarded), same bits.
+template <bool U = false>
 __device__ __forceinline__ void light_dir_dist(const RgLightDev &l, V3 p, V3 &dir, double &dist) {
     if (l.kind == RG_LIGHT_DIRECTIONAL) {
         dir = v3(l.dn[0], l.dn[1], l.dn[2]);  // normalize(-direction), precomputed
@@ -213,9 +216,16 @@ __device__ __forceinline__ void light_dir_dist(const RgLightDev &l, V3 p, V3 &di
         return;
     }
     V3 v = sub(v3(l.v[0], l.v[1], l.v[2]), p);
-    double m = sqrt(dot(v, v));
-    dir = scl(v, 1.0 / m);
-    dist = m;
+    if constexpr (U) {
+        double m, inv;
+        sqrt_rcp_guarded(dot(v, v), m, inv);
+        dir = scl(v, inv);
+        dist = m;
+    } else {
+        double m = sqrt(dot(v, v));
+        dir = scl(v, 1.0 / m);
+        dist = m;
+    }
 }
 
 // lights.rs:46-58

@@ -69,6 +69,48 @@ extern "C" hipError_t rg_launch_camera_check(const RgKernelArgs *a, unsigned lon
     return hipGetLastError();
 }
 
+// rg_debug_unscaled_check: the guarded primitives of rg_k_math.h (the PLAIN kernels' sqrt, 1.0 / x and
+// a / b: unscaled for the lanes whose operands admit it, the compiler's own under a wave-uniform branch
+// for the rest) against the compiler's sqrt and division, one lane per operand.  Two kernels, so that
+// neither side's code can be merged with the other's: the first stores the guarded results, the
+// second computes the plain ones and counts the operands whose results differ in any bit.
+// op: 0 sqrt(a), 1 1.0 / a, 2 a / b, 3 sqrt(a) and 1.0 / sqrt(a) from one admission (out[i], out[n + i]).
+__global__ __launch_bounds__(256) void rg_unscaled_guarded_kernel(int op, const double *a, const double *b, uint32_t n,
+                                                                  double *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double x = a[i];
+    if (op == 0) out[i] = sqrt_guarded(x);
+    else if (op == 1) out[i] = rcp_guarded(x);
+    else if (op == 2) out[i] = div_guarded(x, b[i]);
+    else sqrt_rcp_guarded(x, out[i], out[n + i]);
+}
+__global__ __launch_bounds__(256) void rg_unscaled_compare_kernel(int op, const double *a, const double *b, uint32_t n,
+                                                                  const double *out, unsigned long long *bad) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const double x = a[i];
+    bool same;
+    if (op == 0) same = __double_as_longlong(sqrt(x)) == __double_as_longlong(out[i]);
+    else if (op == 1) same = __double_as_longlong(1.0 / x) == __double_as_longlong(out[i]);
+    else if (op == 2) same = __double_as_longlong(x / b[i]) == __double_as_longlong(out[i]);
+    else {
+        const double m = sqrt(x);
+        same = __double_as_longlong(m) == __double_as_longlong(out[i]) &&
+               __double_as_longlong(1.0 / m) == __double_as_longlong(out[n + i]);
+    }
+    if (!same) atomicAdd(bad, 1ull);
+}
+
+extern "C" hipError_t rg_launch_unscaled_check(int op, const double *a, const double *b, uint32_t n, double *out,
+                                               unsigned long long *bad, hipStream_t stream) {
+    if (n == 0 || op < 0 || op > 3) return hipErrorInvalidValue;
+    const dim3 grid((n + 255u) / 256u);
+    hipLaunchKernelGGL(rg_unscaled_guarded_kernel, grid, dim3(256), 0, stream, op, a, b, n, out);
+    hipLaunchKernelGGL(rg_unscaled_compare_kernel, grid, dim3(256), 0, stream, op, a, b, n, out, bad);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- launchers
 // Occupancy of one kernel instantiation on the CURRENT device, cached per
 // (device, kernel, dynamic LDS): hipFuncSetAttribute and the occupancy query

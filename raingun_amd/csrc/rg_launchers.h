@@ -26,6 +26,11 @@ extern "C" hipError_t rg_launch_trace(const RgKernelArgs *a, const double *rays,
 // rg_kernels.hip: *bad (device, zeroed by the caller) += the pixels of the a->width x a->height frame whose
 // camera direction differs between the general and the PLAIN kernels' arithmetic (rg_debug_camera_check).
 extern "C" hipError_t rg_launch_camera_check(const RgKernelArgs *a, unsigned long long *bad, hipStream_t stream);
+// *bad (zeroed by the caller) += the operands a[i] (and b[i], op 2) for which the PLAIN kernels' guarded
+// sqrt / reciprocal / division differs from the compiler's in any bit (rg_debug_unscaled_check).
+// out: scratch for 2 n doubles.
+extern "C" hipError_t rg_launch_unscaled_check(int op, const double *a, const double *b, uint32_t n, double *out,
+                                               unsigned long long *bad, hipStream_t stream);
 // rg_resolve.hip: the resolve of adaptive anti-aliasing over rows x width output pixels: pixels
 // whose mask byte is non-zero become the box resolve of their k x k samples of `in` (nullable:
 // none), the others keep rgba and get their rgb (nullable) clamped in place.

@@ -98,6 +98,9 @@ __global__ __launch_bounds__(64 * rg_block_waves(LBT, WPS), rg_min_waves_per_eu(
 void rg_render_kernel(RgKernelArgs a) {
     using K = RenderCfg<MAXD, LSPH, LCOLD, WPS, LBT, F32F, BVH, TASKS, TPW, HF, SPARSE, PLAIN>;
     constexpr int LB = K::lights_per_batch;  // shorthand: the per-light loops below are unrolled over it
+    // PLAIN: the spherical lights' sqrt and 1.0 / m without their range scaling, per lane admitted
+    // (rg_k_math.h sqrt_rcp_guarded)
+    constexpr bool UL = PLAIN && RG_PLAIN_ULIGHT != 0;
 #ifdef RG_WAVE_TIMES  // diagnostic: per-wave start (before staging), staged, end (100 MHz ticks), tiles
     const unsigned long long t_wave0 = wall_clock64();
     uint32_t wt_tiles = 0;
@@ -388,7 +391,7 @@ void rg_render_kernel(RgKernelArgs a) {
                                 if (l < n_lights) {
                                     const RgLightDev L = T.lights[l];
                                     if (L.kind != RG_LIGHT_DIRECTIONAL) RG_REGION(RGR_LIGHT_SPH);
-                                    light_dir_dist(L, h, sb.d[l], sb.ld[l]);
+                                    light_dir_dist<UL>(L, h, sb.d[l], sb.ld[l]);
                                     park[64 * (PK_PP + l)] = fmaxf((float)dot(n, sb.d[l]), 0.0f);  // rendering.rs:161-162
                                     park[64 * (PK_LIN + l)] = light_intensity(L, h);               // pure; used if lit
                                     occl_full |= 1u << l;
@@ -547,7 +550,7 @@ void rg_render_kernel(RgKernelArgs a) {
                             const RgLightDev L = T.lights[li + 1 + k];
                             V3 ldir;
                             double ldist;
-                            light_dir_dist(L, hp, ldir, ldist);  // as at setup: same bits
+                            light_dir_dist<UL>(L, hp, ldir, ldist);  // as at setup: same bits
                             float inten = !((fan_bits >> k) & 1u) ? light_intensity(L, hp) : 0.0f;
                             float power = fmaxf((float)dot(hn, ldir), 0.0f) * inten;
                             C3 lc = cscl(cscl(c3(L.color[0], L.color[1], L.color[2]), power), refl);
@@ -564,7 +567,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #pragma unroll
                     for (int l = 0; l < LB; ++l) {
                         if (li + l < a.n_lights) {
-                            light_dir_dist(T.lights[li + l], hp, sb.d[l], sb.ld[l]);
+                            light_dir_dist<UL>(T.lights[li + l], hp, sb.d[l], sb.ld[l]);
                             occl_full |= 1u << l;
                             n_shadow++;
                         } else {
@@ -883,7 +886,7 @@ void rg_render_kernel(RgKernelArgs a) {
                             q.o = oso;  // hit + n * bias (rendering.rs:148)
                             hdepth = ohd;
                             pixel = opix;  // error reports name the owner's pixel
-                            light_dir_dist(T.lights[oli + 1 + k], hp, sb.d[0], sb.ld[0]);
+                            light_dir_dist<UL>(T.lights[oli + 1 + k], hp, sb.d[0], sb.ld[0]);
                             li = oli + 1 + k;  // the light this helper traces (its li is unused otherwise)
                             mode = MODE_SHADOW_H;
                         }

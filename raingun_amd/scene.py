@@ -334,6 +334,23 @@ class DeviceScene:
                                                     C.byref(admitted)))
         return int(bad.value), admitted.value == 1
 
+    def unscaled_check(self, op: int, a, b=None) -> int:
+        """rg_debug_unscaled_check: the operands (float64 arrays; b for op 2, a / b) for which the PLAIN
+        kernels' guarded sqrt (op 0), 1 / a (1), a / b (2) or sqrt and 1 / sqrt (3) differ from the
+        compiler's operations in any bit."""
+        import numpy as np
+
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        bp = None
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float64)
+            assert b.shape == a.shape
+            bp = b.ctypes.data_as(C.c_void_p)
+        bad = C.c_uint64(0)
+        _abi.check(_abi.lib().rg_debug_unscaled_check(self.handle, int(op), a.ctypes.data_as(C.c_void_p), bp, a.size,
+                                                      C.byref(bad)))
+        return int(bad.value)
+
     def bvh_info(self) -> _abi.rg_bvh_info:
         info = _abi.rg_bvh_info()
         _abi.check(_abi.lib().rg_debug_bvh_info(self.handle, C.byref(info)))
