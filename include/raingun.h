@@ -184,7 +184,7 @@ rg_status rg_camera_look_at(const double eye[3], const double target[3], const d
 /* The camera of every later render of `scene` that goes through the tiled launch: rg_render_image,
  * rg_render_tiles / _async / _pipelined, rg_render_stream, rg_render_image_aa / rg_render_aa_async,
  * rg_render_image_aa_adaptive / rg_render_aa_adaptive, rg_render_multi (both modes; its replicas
- * follow) and rg_frames_*.  rg_trace is unaffected; error codes and error_pixel keep their meaning.
+ * follow) and rg_frames_*, and of rg_render_aov / rg_render_aov_async.  rg_trace is unaffected; error codes and error_pixel keep their meaning.
  * NULL restores the reference's view, and with it exactly the kernels the scene launched before.
  * The camera is host state: it is read when a launch is enqueued and travels by value in the
  * kernel's arguments, so changing it between launches on different streams needs no
@@ -352,6 +352,42 @@ rg_status rg_render_stream(const rg_scene *scene, uint32_t width, uint32_t heigh
  * hit distance and body[i] the body index, or body[i] = -1 on a miss. */
 rg_status rg_trace(const rg_scene *scene, const double *rays, uint32_t n,
                    double *dist, int32_t *body);
+
+/* AOV layers (auxiliary output variables, a G-buffer): what lies under each pixel.  The ray of pixel
+ * (x, y) is exactly the ray rg_render_image traces for it: Ray::create_prime (ray.rs:37-54), or the
+ * ray of rg_scene_set_camera.  One ray per pixel, at depth 0, whatever the scene's max depth:
+ * rays.primary == the pixels rendered, shadow and secondary are 0.  Layers are row-major. */
+typedef struct rg_aov {          /* every member nullable; at least one non-null */
+    int32_t *body;               /* YAML index of the primary hit, -1 on a miss                      */
+    double  *depth;              /* its Scene::trace distance t (scene.rs:34-39), +inf on a miss      */
+    float   *normal;             /* 3 per pixel: (f32) of each f64 component of surface_normal(body, hit),
+                                    hit = origin + direction * t (rendering.rs get_color); the reference's
+                                    geometric normal, never flipped; 0,0,0 on a miss                   */
+    float   *uv;                 /* 2 per pixel: texture_coords(body, hit) before the material's offsets;
+                                    0,0 on a miss and for AABBs                                        */
+    float   *albedo;             /* 3 per pixel: Material::color at the hit (texture texel or flat colour,
+                                    material.rs:62-68); the scene's default_color on a miss            */
+} rg_aov;
+
+/* Blocking whole-frame AOV render into host buffers (pageable or pinned) of width*height elements
+ * per requested layer.  The frame is delivered on every device error: RG_ERR_NAN_DISTANCE where
+ * rg_trace raises it; RG_ERR_AABB_NORMAL when `normal` is requested and surface_normal finds no face
+ * (bodies.rs:324; that pixel's normal is 1,0,0 as in get_color); stats->error_pixel is the lowest
+ * failing pixel.  RG_ERR_PORTRAIT for width < height; RG_ERR_INVALID_ARGUMENT for a null scene or
+ * `out`, all five pointers null, zero sizes or 2^32 pixels or more.  `stats` may be NULL. */
+rg_status rg_render_aov(const rg_scene *scene, uint32_t width, uint32_t height,
+                        const rg_aov *out /* host */, rg_stats *stats);
+
+/* Device-resident rg_render_aov of the tiles selected by `tiling`, with rg_render_tiles_async's packing
+ * and stream contract: `dev` holds device pointers on the scene's device (rg_tiling_rows x width
+ * elements per requested layer); each stream has its own launch context, launches of one scene on
+ * distinct streams may be in flight together, the camera is read at enqueue and travels by value, and
+ * the call is asynchronous unless `stats` is non-NULL (then it synchronises `stream`; without it
+ * rg_stream_status reports device errors).  Padding rows of a partial last tile hold body -1, depth
+ * +inf and zeros in the other layers.  Also RG_ERR_INVALID_ARGUMENT for a null or bad tiling. */
+rg_status rg_render_aov_async(const rg_scene *scene, uint32_t width, uint32_t height,
+                              const rg_tiling *tiling, const rg_aov *dev /* device */,
+                              void *stream, rg_stats *stats);
 
 /* Single-process multi-GPU render (SURVEY.md §8(b),(e)): the same frame as
  * rg_render_image, split over `ngpus` devices -- the scene's device first,

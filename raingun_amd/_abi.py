@@ -114,6 +114,11 @@ class rg_camera(C.Structure):
                 ("forward", C.c_double * 3)]
 
 
+class rg_aov(C.Structure):  # device or host pointers, each nullable (include/raingun.h)
+    _fields_ = [("body", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("uv", C.c_void_p),
+                ("albedo", C.c_void_p)]
+
+
 class rg_bvh_info(C.Structure):  # include/raingun_debug.h
     _fields_ = [("built", C.c_int32), ("enabled", C.c_int32), ("nodes", C.c_int32), ("leaves", C.c_int32),
                 ("depth", C.c_int32), ("margin", C.c_float), ("origin_bound", C.c_float), ("lane_stack", C.c_int32),
@@ -150,6 +155,8 @@ EXPORTED_SYMBOLS = (
     "rg_edge_mask",
     "rg_camera_look_at",
     "rg_scene_set_camera",
+    "rg_render_aov",
+    "rg_render_aov_async",
 )
 # include/raingun_debug.h
 DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "rg_debug_counters",
@@ -311,6 +318,12 @@ def _declare(lib: C.CDLL) -> None:
         lib.rg_edge_mask.restype = C.c_int32
         lib.rg_edge_mask.argtypes = [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                      P(C.c_uint32)]
+    if hasattr(lib, "rg_render_aov"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
+        lib.rg_render_aov.restype = C.c_int32
+        lib.rg_render_aov.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_aov), P(rg_stats)]
+        lib.rg_render_aov_async.restype = C.c_int32
+        lib.rg_render_aov_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_tiling), P(rg_aov), C.c_void_p,
+                                            P(rg_stats)]
     lib.rg_frames_status.restype = C.c_int32
     lib.rg_frames_status.argtypes = [C.c_void_p, P(C.c_int32)]
     if hasattr(lib, "rg_frames_set_batch"):  # absent from pre-round-3 builds

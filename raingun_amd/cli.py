@@ -1,7 +1,7 @@
 """`raingun` command line, mirroring the reference's src/main.rs + src/render.rs.
 
     python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
-                              [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [-o FILE] FILE
+                              [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aov LAYERS] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
@@ -17,7 +17,13 @@ accepted and has no effect.  `--eye X,Y,Z --look-at X,Y,Z [--up X,Y,Z]` (not in
 the reference, whose view is from the origin down -z) move the camera
 (rg_scene_set_camera): --up defaults to 0,1,0, --eye without --look-at looks
 down -z from the eye; a malformed triple or a rejected look-at ends the run
-like any other bad flag value.  The scene file has no camera key.  The
+like any other bad flag value.  The scene file has no camera key.
+`--aov LAYERS` (not in the reference; a comma list of body, depth, normal, uv,
+albedo, or `all`) also writes, next to `-o out.png`, `out.<layer>.png` for each
+named layer: what lies under each pixel (rg_render_aov), as the pictures of
+raingun_amd/aov.py visualize.  It honours the size flags and the camera;
+--samples and --adaptive affect only the beauty frame, the layers stay one ray
+per pixel.  Without --aov nothing changes, the timing line included.  The
 render itself runs on the GPU (rg_render_image); the scene is loaded and the
 PNG written by the native host layer (libraingun_host.so), and the timing line matches
 print_render_message (render.rs:218-244).  `--preview` (piston window) is not
@@ -34,6 +40,7 @@ from typing import List, Optional
 
 import numpy as np
 
+from . import aov
 from .camera import Camera, camera_from_flags, parse_triple
 
 
@@ -45,6 +52,7 @@ class RenderOptions:          # render.rs:32-46
     samples: int = 1          # N x N rays per pixel (--samples; not in the reference)
     adaptive: Optional[int] = None  # contrast threshold of adaptive anti-aliasing (--adaptive)
     camera: Optional[Camera] = None  # --eye / --look-at / --up (not in the reference)
+    aov: tuple = ()           # layers of --aov, in aov.LAYERS order (not in the reference)
 
 
 class _LastWins(argparse.Action):
@@ -80,6 +88,9 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("--look-at", dest="look_at", metavar="X,Y,Z",
                    help="Point the camera looks at (default: straight down -z from the eye).")
     p.add_argument("--up", metavar="X,Y,Z", help="Up hint of --look-at (default 0,1,0).")
+    p.add_argument("--aov", metavar="LAYERS",
+                   help="Also write FILENAME.<layer>.png for each of a comma list of body, depth, normal, uv, "
+                        "albedo (or all).")
     p.add_argument("input", metavar="FILE", help="The scene definition file, in YAML format.")
     return p
 
@@ -95,6 +106,11 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
         if not 0 <= o.adaptive <= 256:
             raise SystemExit("adaptive must be between 0 and 256")
     o.camera = _parse_camera(ns)
+    if ns.aov is not None:
+        try:
+            o.aov = aov.parse_layers(ns.aov)
+        except ValueError:
+            raise SystemExit("Could not parse aov") from None
     if ns.draft:
         o.max_recursion_depth = 4
     elif ns.hd:
@@ -209,6 +225,10 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
     t1 = time.perf_counter()
     output_path.write_bytes(encode_png(img))     # render.rs:58
     t2 = time.perf_counter()
+    if opts.aov:  # out.png -> out.<layer>.png, one ray per pixel whatever --samples says
+        layers = ds.render_aov(opts.width, opts.height, opts.aov)
+        for name in opts.aov:
+            output_path.with_suffix(f".{name}.png").write_bytes(encode_png(aov.visualize(name, layers[name])))
     ds.close()
     print(f"{input_path}\t→\t{output_path}\t({format_duration(int((t1 - t0) * 1000))} render, "
           f"{format_duration(int((t2 - t1) * 1000))} write)")

@@ -1,5 +1,5 @@
-// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip, rg_tile_order_camera.hip, rg_resolve.hip and rg_edge.hip
-// define for the host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  The defining files
+// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip, rg_tile_order_camera.hip, rg_resolve.hip, rg_edge.hip
+// and rg_aov.hip define for the host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  The defining files
 // include this header too, so the compiler checks every signature against it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +23,15 @@ extern "C" hipError_t rg_launch_resolve(const float *in, uint32_t width, uint32_
                                         float *rgb, hipStream_t stream);
 extern "C" hipError_t rg_launch_trace(const RgKernelArgs *a, const double *rays, uint32_t n, double *dist,
                                       int32_t *body, hipStream_t stream);
+// rg_aov.hip: the AOV layers of the launch's pixels (rg_aov of include/raingun.h as device pointers, each
+// nullable; packing of a->rgba's rows).  Reads of `a` the scene's tables, the frame, tiling and camera
+// members, tile_wlog (the wave's tile shape) and the counter sets; primary rays count into a->counters[0].
+struct RgAovOut {
+    int32_t *body;
+    double *depth;
+    float *normal, *uv, *albedo;
+};
+extern "C" hipError_t rg_launch_aov(const RgKernelArgs *a, const RgAovOut *o, hipStream_t stream);
 // rg_kernels.hip: *bad (device, zeroed by the caller) += the pixels of the a->width x a->height frame whose
 // camera direction differs between the general and the PLAIN kernels' arithmetic (rg_debug_camera_check).
 extern "C" hipError_t rg_launch_camera_check(const RgKernelArgs *a, unsigned long long *bad, hipStream_t stream);

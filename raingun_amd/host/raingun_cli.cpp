@@ -3,8 +3,13 @@
 // the HIP renderer (libraingun_hip.so: rg_render_image).
 //
 //   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
-//           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [-o FILE] [--gpu N] FILE
+//           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aov LAYERS] [-o FILE] [--gpu N] FILE
 //
+// --aov LAYERS (not in the reference): a comma list of body, depth, normal, uv, albedo, or `all`.  Next to
+// `-o out.png` the run also writes `out.<layer>.png` for each named layer: what lies under each pixel
+// (rg_render_aov), as the pictures raingun_amd/aov.py states in numpy (visualize): every cast the Rust
+// `f32 as u8`, alpha 255.  It honours the size flags and the camera; --samples and --adaptive affect only
+// the beauty frame.  An unknown layer name is an argument error.  Without --aov nothing changes.
 // --eye / --look-at / --up (not in the reference, whose view is from the origin down -z): the camera
 // (rg_camera_look_at, rg_scene_set_camera).  --up defaults to 0,1,0; --eye without --look-at looks down
 // -z from the eye; a malformed triple or a rejected look-at is an argument error.  No camera key in the YAML.
@@ -21,6 +26,7 @@
 // Rust's panic status; argument errors exit with 1 like clap.  `--preview`
 // (piston window) has no display on an MI355X node: it renders without one.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +56,7 @@ const char *kHelp =
     "        --eye <X,Y,Z>          Camera position (default 0,0,0).\n"
     "        --look-at <X,Y,Z>      Point the camera looks at (default: straight down -z from the eye).\n"
     "        --up <X,Y,Z>           Up hint of --look-at (default 0,1,0).\n"
+    "        --aov <LAYERS>         Also write FILENAME.<layer>.png for each of body,depth,normal,uv,albedo (or all).\n"
     "        --adaptive <T>         Adaptive anti-aliasing: the N x N rays only where the 1-sample frame's contrast is at least T (0..256).\n"
     "        --gpu <N>              HIP device to render on (default 0).\n"
     "    -h, --height <PIXELS>      Height of output image.\n"
@@ -73,7 +80,7 @@ const char *kHelp =
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
     const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr,
-               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr;
+               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr;
     int gpu = 0;
 };
 
@@ -86,7 +93,11 @@ struct RenderOptions {  // render.rs:32-46
     uint32_t max_recursion_depth = 0;
     bool has_camera = false;  // --eye / --look-at / --up
     rg_camera camera{};
+    bool aov[5] = {false, false, false, false, false};  // --aov: body, depth, normal, uv, albedo
+    bool any_aov = false;
 };
+
+const char *const kLayers[5] = {"body", "depth", "normal", "uv", "albedo"};
 
 bool parse_triple(const char *s, double out[3]) {  // "X,Y,Z": three finite numbers, nothing else
     if (!s) return false;
@@ -146,6 +157,7 @@ Args parse_args(int argc, char **argv) {
             else if (name == "eye") a.eye = take_value(i, "--eye <X,Y,Z>", val);
             else if (name == "look-at") a.look_at = take_value(i, "--look-at <X,Y,Z>", val);
             else if (name == "up") a.up = take_value(i, "--up <X,Y,Z>", val);
+            else if (name == "aov") a.aov = take_value(i, "--aov <LAYERS>", val);
             else if (val) clap_error("Found argument '" + std::string(arg) + "' which wasn't expected, or isn't valid in this context");
             else if (name == "4k") { a.uhd = true; a.hd = false; }   // overrides_with("hd")
             else if (name == "hd") { a.hd = true; a.uhd = false; }   // overrides_with("4k")
@@ -181,6 +193,20 @@ RenderOptions options_from(const Args &a) {  // main.rs:70-96
         if (o.adaptive > 256)
             clap_error(std::string("Invalid value for '--adaptive <T>': ") + a.adaptive + " is not between 0 and 256");
         o.has_adaptive = true;
+    }
+    if (a.aov) {
+        const std::string spec = a.aov;
+        for (size_t pos = 0; spec != "all";) {
+            const size_t comma = spec.find(',', pos);
+            const std::string name = spec.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+            int k = 0;
+            while (k < 5 && name != kLayers[k]) ++k;
+            if (k == 5) clap_error(std::string("Invalid value for '--aov <LAYERS>': ") + a.aov);
+            o.aov[k] = true;
+            if (comma == std::string::npos) break;
+            pos = comma + 1;
+        }
+        for (int k = 0; k < 5; ++k) o.any_aov |= (o.aov[k] |= spec == "all");
     }
     if (a.up && !a.look_at) clap_error("The argument '--up <X,Y,Z>' needs '--look-at <X,Y,Z>'");
     if (a.eye || a.look_at) {
@@ -236,6 +262,67 @@ bool with_png_extension(const std::string &in, std::string &out) {
     return true;
 }
 
+// Path::with_suffix(".<layer>.png") of the output file: out.png -> out.body.png
+std::string with_layer_extension(const std::string &path, const char *layer) {
+    const size_t slash = path.rfind('/');
+    const size_t name0 = slash == std::string::npos ? 0 : slash + 1;
+    const size_t dot = path.rfind('.');
+    const std::string stem = (dot == std::string::npos || dot <= name0) ? path : path.substr(0, dot);
+    return stem + "." + layer + ".png";
+}
+
+// Rust `f32 as u8`: truncate, saturate, NaN -> 0.
+uint8_t f32_to_u8(float v) {
+    if (!(v > 0.0f)) return 0;
+    if (v >= 255.0f) return 255;
+    return (uint8_t)v;
+}
+
+// The picture of layer k (raingun_amd/aov.py visualize): n pixels -> RGBA8.
+void visualize(int k, size_t n, const int32_t *body, const double *depth, const float *f, uint8_t *px) {
+    double tmin = 0.0, tmax = 0.0;
+    bool any = false;
+    if (k == 1)
+        for (size_t i = 0; i < n; ++i)
+            if (std::isfinite(depth[i])) {
+                tmin = any ? std::fmin(tmin, depth[i]) : depth[i];
+                tmax = any ? std::fmax(tmax, depth[i]) : depth[i];
+                any = true;
+            }
+    for (size_t i = 0; i < n; ++i) {
+        uint8_t *p = px + 4 * i;
+        p[0] = p[1] = p[2] = 0;
+        p[3] = 255;
+        if (k == 0) {
+            if (body[i] < 0) continue;
+            const uint32_t h = (uint32_t)(body[i] + 1) * 2654435761u;
+            p[0] = (uint8_t)(h >> 24);
+            p[1] = (uint8_t)(h >> 16);
+            p[2] = (uint8_t)(h >> 8);
+        } else if (k == 1) {
+            if (!std::isfinite(depth[i])) continue;
+            const double v = tmax == tmin ? 1.0 : 1.0 - (depth[i] - tmin) / (tmax - tmin);
+            const float g = (float)v;
+            p[0] = p[1] = p[2] = f32_to_u8(g * 255.0f);
+        } else if (k == 2) {
+            const float *c = f + 3 * i;
+            if (c[0] == 0.0f && c[1] == 0.0f && c[2] == 0.0f) continue;
+            for (int j = 0; j < 3; ++j) {
+                const float half = c[j] * 0.5f;
+                const float shifted = half + 0.5f;
+                p[j] = f32_to_u8(shifted * 255.0f);
+            }
+        } else if (k == 3) {
+            for (int j = 0; j < 2; ++j) {
+                const float frac = f[2 * i + j] - std::floor(f[2 * i + j]);
+                p[j] = f32_to_u8(frac * 255.0f);
+            }
+        } else {
+            for (int j = 0; j < 3; ++j) p[j] = f32_to_u8(f[3 * i + j] * 255.0f);  // color.rs:32-37
+        }
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -276,6 +363,24 @@ int main(int argc, char **argv) {
     st = rgh_png_write(output.c_str(), rgba.data(), opts.width, opts.height);  // render.rs:58
     auto t2 = std::chrono::steady_clock::now();
     if (st != RGH_OK) panic(rgh_last_error());
+    if (opts.any_aov) {  // after the beauty frame and outside its timing line
+        const size_t n = (size_t)opts.width * opts.height;
+        std::vector<int32_t> body(opts.aov[0] ? n : 0);
+        std::vector<double> depth(opts.aov[1] ? n : 0);
+        std::vector<float> normal(opts.aov[2] ? 3 * n : 0), uv(opts.aov[3] ? 2 * n : 0), albedo(opts.aov[4] ? 3 * n : 0);
+        const rg_aov layers = {opts.aov[0] ? body.data() : nullptr, opts.aov[1] ? depth.data() : nullptr,
+                               opts.aov[2] ? normal.data() : nullptr, opts.aov[3] ? uv.data() : nullptr,
+                               opts.aov[4] ? albedo.data() : nullptr};
+        st = rg_render_aov(scene, opts.width, opts.height, &layers, nullptr);
+        if (st != RG_OK) panic(rg_status_string(st));
+        const float *planes[5] = {nullptr, nullptr, normal.data(), uv.data(), albedo.data()};
+        for (int k = 0; k < 5; ++k) {
+            if (!opts.aov[k]) continue;
+            visualize(k, n, body.data(), depth.data(), planes[k], rgba.data());
+            st = rgh_png_write(with_layer_extension(output, kLayers[k]).c_str(), rgba.data(), opts.width, opts.height);
+            if (st != RGH_OK) panic(rgh_last_error());
+        }
+    }
     rg_scene_destroy(scene);
     rgh_scene_free(loaded);
 

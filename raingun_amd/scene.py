@@ -26,7 +26,7 @@ from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _abi
+from . import _abi, aov
 from .camera import Camera
 from .color import Color
 
@@ -495,6 +495,42 @@ class DeviceScene:
         _abi.check(status, "rg_render_tiles")
         return (rgba, rgb) if want_rgb else rgba
 
+    def render_aov(self, width: int, height: int, layers=aov.LAYERS, stats: Optional[_abi.rg_stats] = None) -> dict:
+        """rg_render_aov: the AOV layers of the frame rg_render_image renders (raingun_amd/aov.py), one
+        primary ray per pixel through the scene's camera.  Returns {layer name: numpy array}.  A device
+        error (the reference's panics) raises RaingunError, as render_image does; `stats` then names
+        the first failing pixel."""
+        layers = aov.parse_layers(layers)
+        out = {n: np.empty(aov.layer_shape(n, height, width), dtype=aov.DTYPES[n]) for n in layers}
+        v = _abi.rg_aov(**{n: out[n].ctypes.data for n in layers})
+        st = stats if stats is not None else _abi.rg_stats()
+        _abi.check(_abi.lib().rg_render_aov(self.handle, width, height, C.byref(v), C.byref(st)), "rg_render_aov")
+        return out
+
+    def render_aov_tiles(self, width: int, height: int, tile_rows: int = 0, stride: int = 1, offset: int = 0,
+                         layers=aov.LAYERS, stream: int = 0, stats: Optional[_abi.rg_stats] = None,
+                         out: Optional[dict] = None) -> dict:
+        """rg_render_aov_async: the layers of the tiles a tiling selects (render_tiles' packing), in
+        device memory, enqueued on `stream` (a hipStream_t value).  Returns {layer name: torch tensor on
+        this scene's device}; `out` supplies the tensors to write into.  Asynchronous unless `stats` is
+        given: the caller synchronises `stream` before reading the tensors."""
+        import torch
+
+        layers = aov.parse_layers(layers)
+        t = _abi.rg_tiling(tile_rows or height, stride, offset)
+        rows = _abi.lib().rg_tiling_rows(height, C.byref(t))
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            tt = {np.int32: torch.int32, np.float64: torch.float64, np.float32: torch.float32}
+            out = {n: torch.empty(aov.layer_shape(n, rows, width), dtype=tt[aov.DTYPES[n]], device=dev) for n in layers}
+        for n in layers:
+            assert tuple(out[n].shape) == aov.layer_shape(n, rows, width) and out[n].is_contiguous(), n
+        v = _abi.rg_aov(**{n: out[n].data_ptr() for n in layers})
+        status = _abi.lib().rg_render_aov_async(self.handle, width, height, C.byref(t), C.byref(v), C.c_void_p(stream),
+                                                C.byref(stats) if stats is not None else None)
+        _abi.check(status, "rg_render_aov_async")
+        return out
+
     def trace(self, rays: np.ndarray):
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         n = rays.shape[0]
@@ -532,6 +568,16 @@ class Scene:                   # scene.rs:11-31
             if samples != 1:
                 return ds.render_image_aa(width, height, samples)
             return ds.render_image(width, height)
+        finally:
+            ds.close()
+
+    # the AOV layers of render_image's frame (rg_render_aov; raingun_amd/aov.py): {layer name: numpy array}
+    def render_aov(self, width: int, height: int, device: int = 0, layers=aov.LAYERS,
+                   camera: Optional[Camera] = None) -> dict:
+        ds = DeviceScene(self, device)
+        try:
+            ds.set_camera(camera)
+            return ds.render_aov(width, height, layers)
         finally:
             ds.close()
 

@@ -1,13 +1,14 @@
 """Per-instantiation register/scratch summary of rg_render_kernel.
 
-    python scripts/resources.py [--camera] [extra hipcc flags...]
+    python scripts/resources.py [--camera | --aov] [extra hipcc flags...]
 
 Compiles the three depth-8 files (rg_render_heavy_d8_host.hip, rg_render_light_d8.hip,
 rg_render_heavy_d8.hip) with the library's flags and -Rpass-analysis=kernel-resource-usage and prints VGPRs, spilled VGPRs, scratch bytes per lane, occupancy and static LDS for the
 MAXD = 8 instantiations (the ones the bench configurations run; "host": the
 host-frame ones, "tpw=-1": the light path's persistent single launches).
 --camera: instead, the camera family (MAXD = -1: rg_render_{light,heavy}_camera{,_sparse}.hip) beside
-the MAXD = 0 kernels it derives from (rg_render_{light,heavy}_{d0,sparse}.hip), MAXD printed first."""
+the MAXD = 0 kernels it derives from (rg_render_{light,heavy}_{d0,sparse}.hip), MAXD printed first.
+--aov: instead, the instantiations of rg_aov_kernel (rg_aov.hip) and the out-of-line sphere_uv they call."""
 import re
 import subprocess
 import sys
@@ -23,6 +24,10 @@ if "--camera" in sys.argv[1:]:
     UNITS = ["rg_render_light_d0", "rg_render_light_camera", "rg_render_light_sparse", "rg_render_light_camera_sparse",
              "rg_render_heavy_d0", "rg_render_heavy_camera", "rg_render_heavy_sparse", "rg_render_heavy_camera_sparse"]
     SHOW = (0, -1)
+AOV = "--aov" in sys.argv[1:]
+if AOV:
+    sys.argv.remove("--aov")
+    UNITS = ["rg_aov"]
 procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
                            "-fno-fast-math", "-fPIC", "-c", u + ".hip", "-o", f"/tmp/{u}_res.o",
                            "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:]],
@@ -43,7 +48,14 @@ for line in remarks:
     m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None:
         cur[m.group(1)] = int(m.group(2))
-for r in rows:
+for r in rows if AOV else []:
+    m = re.match(r"_Z13rg_aov_kernelILb(\d)ELb(\d)ELb(\d)ELb(\d)EE", r["name"])
+    if m is None and "sphere_uv" not in r["name"]:
+        continue
+    what = "sphere_uv (out of line)" if m is None else "rg_aov_kernel<CAMERA %s, F32F %s, BVH %s, SHADE %s>" % m.groups()
+    print(f"{what:52s}  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}"
+          f"  scratch {r.get('ScratchSize [bytes/lane]')} B/lane  occ {r.get('Occupancy [waves/SIMD]')}  lds {r.get('LDS Size [bytes/block]')}")
+for r in [] if AOV else rows:
     k = parse(r["name"])
     if k is None or k["MAXD"] not in SHOW:
         continue
