@@ -149,6 +149,29 @@ rg_status rg_debug_counter_words(const rg_scene *scene, int32_t first, int32_t n
  * kernel.  A word the launcher writes; results are identical either way. */
 rg_status rg_debug_last_plain(const rg_scene *scene, int32_t *plain);
 
+/* Shadow mask volume of the PLAIN light kernels (rg_shadow_vol.cpp): a grid over the scene, built by
+ * rg_scene_create for scenes of spheres and planes only (1..16 bodies of each kind at most, 1..3
+ * lights, every parameter finite and at most 2^20 in magnitude), whose cells name the bodies that
+ * could occlude a light from a shadow origin there; a wave tests only the bodies its lanes' cells
+ * name.  rg_debug_set_shadow_volume(0): the scene's launches pass no volume and test every body
+ * (1, the default: the volume where one was built).  Results are identical either way.
+ * rg_debug_shadow_volume_info: whether a volume was built and is switched on, its cells per axis,
+ * device bytes, build time on the host and the share of set bits (set / (cells x bodies)).
+ * rg_debug_last_shadow_volume: *used = 1 if the scene's latest render launch ran a PLAIN kernel
+ * with the volume, else 0. */
+typedef struct rg_shadow_volume_info {
+    int32_t built;
+    int32_t enabled;
+    int32_t g;
+    int32_t pad;
+    int64_t bytes;
+    double build_ms;
+    double set_share;
+} rg_shadow_volume_info;
+rg_status rg_debug_set_shadow_volume(rg_scene *scene, int32_t on);
+rg_status rg_debug_shadow_volume_info(const rg_scene *scene, rg_shadow_volume_info *info);
+rg_status rg_debug_last_shadow_volume(const rg_scene *scene, int32_t *used);
+
 /* The PLAIN light kernels compute the camera ray's two quotients from host reciprocals and its
  * length without range scaling, after the launcher has checked the frame size column by column and
  * row by row and bounded the field of view.  rg_debug_set_exact_div(0): the scene's launches behave

@@ -125,6 +125,11 @@ class rg_bvh_info(C.Structure):  # include/raingun_debug.h
                 ("lbuf_bytes", C.c_int64)]
 
 
+class rg_shadow_volume_info(C.Structure):  # include/raingun_debug.h
+    _fields_ = [("built", C.c_int32), ("enabled", C.c_int32), ("g", C.c_int32), ("pad", C.c_int32),
+                ("bytes", C.c_int64), ("build_ms", C.c_double), ("set_share", C.c_double)]
+
+
 TILE_CALLBACK = C.CFUNCTYPE(C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_void_p)
 
 # Every symbol include/raingun.h declares (tests/test_abi.py checks the export table).
@@ -165,6 +170,7 @@ DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "
                  "rg_debug_fail_split_a", "rg_debug_set_host_ring", "rg_debug_set_host_tile_shape", "rg_debug_set_multi", "rg_debug_gather_noop",
                  "rg_debug_counter_words", "rg_debug_set_aa_band_rows",
                  "rg_debug_set_aa_adaptive_timing", "rg_debug_aa_adaptive_info", "rg_debug_last_plain",
+                 "rg_debug_set_shadow_volume", "rg_debug_shadow_volume_info", "rg_debug_last_shadow_volume",
                  "rg_debug_set_exact_div", "rg_debug_camera_check", "rg_debug_unscaled_check")
 # include/raingun_frames.h
 FRAMES_SYMBOLS = ("rg_frames_create", "rg_frames_destroy", "rg_frames_step", "rg_frames_flush", "rg_frames_image",
@@ -258,6 +264,13 @@ def _declare(lib: C.CDLL) -> None:
     if hasattr(lib, "rg_debug_last_plain"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
         lib.rg_debug_last_plain.restype = C.c_int32
         lib.rg_debug_last_plain.argtypes = [C.c_void_p, P(C.c_int32)]
+    if hasattr(lib, "rg_debug_set_shadow_volume"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
+        lib.rg_debug_set_shadow_volume.restype = C.c_int32
+        lib.rg_debug_set_shadow_volume.argtypes = [C.c_void_p, C.c_int32]
+        lib.rg_debug_shadow_volume_info.restype = C.c_int32
+        lib.rg_debug_shadow_volume_info.argtypes = [C.c_void_p, P(rg_shadow_volume_info)]
+        lib.rg_debug_last_shadow_volume.restype = C.c_int32
+        lib.rg_debug_last_shadow_volume.argtypes = [C.c_void_p, P(C.c_int32)]
     if hasattr(lib, "rg_debug_set_exact_div"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
         lib.rg_debug_set_exact_div.restype = C.c_int32
         lib.rg_debug_set_exact_div.argtypes = [C.c_void_p, C.c_int32]

@@ -126,6 +126,7 @@ rg_status rg_render_aov_async(const rg_scene *s, uint32_t width, uint32_t height
     const RgAovOut o{dev->body, dev->depth, dev->normal, dev->uv, dev->albedo};
     cx->last_counters = a.counters;
     cx->last_plain = 0;
+    cx->last_shvol = 0;
     if (stats && !ok(hipEventRecord(cx->ev0, st))) return RG_ERR_DEVICE;
     if (rows > 0) {
         if (!ok(rg_launch_aov(&a, &o, st))) return RG_ERR_DEVICE;

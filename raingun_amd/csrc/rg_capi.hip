@@ -549,6 +549,25 @@ rg_status rg_debug_last_plain(const rg_scene *s, int32_t *plain) {
     return RG_OK;
 }
 
+rg_status rg_debug_set_shadow_volume(rg_scene *s, int32_t on) {
+    if (!s || (on != 0 && on != 1)) return RG_ERR_INVALID_ARGUMENT;
+    s->shvol_enabled = on != 0;
+    return RG_OK;
+}
+
+rg_status rg_debug_shadow_volume_info(const rg_scene *s, rg_shadow_volume_info *info) {
+    if (!s || !info) return RG_ERR_INVALID_ARGUMENT;
+    *info = s->shvol_info;
+    info->enabled = s->shvol_info.built && s->shvol_enabled;
+    return RG_OK;
+}
+
+rg_status rg_debug_last_shadow_volume(const rg_scene *s, int32_t *used) {
+    if (!s || !used || !s->last) return RG_ERR_INVALID_ARGUMENT;
+    *used = s->last->last_shvol;
+    return RG_OK;
+}
+
 rg_status rg_debug_set_exact_div(rg_scene *s, int32_t enable) {
     if (!s || (enable != 0 && enable != 1)) return RG_ERR_INVALID_ARGUMENT;
     s->exact_div = enable != 0;

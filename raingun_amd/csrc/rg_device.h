@@ -246,6 +246,16 @@ struct RgKernelArgs {
     // instantiations keep their argument offsets.
     uint32_t camera;
     double cam_eye[3], cam_right[3], cam_up[3], cam_forward[3];
+    // nullable: the shadow mask volume (rg_shadow_vol.h; PLAIN light kernels only): shvol_g^3 words, the
+    // word of a shadow origin's cell (rg_shadow_vol_cell.h rg_shvol_cell with shvol_inv, shvol_off) has
+    // bit i set if sphere i, bit 16 + j if plane j could occlude a light from there.  Null: every body
+    // is tested.  At the end of the struct: the other instantiations keep their argument offsets.
+    const uint32_t *shvol;
+    uint32_t shvol_g;
+    float shvol_inv, shvol_off;
+    // the struct grows by 32 bytes, so the arguments that follow it in other kernels (rg_trace_kernel,
+    // rg_aov_kernel) keep their 16-byte phase and those kernels their code (profiles/shvol/kernel_isa_diff.txt)
+    uint32_t shvol_pad[3];
 };
 
 __host__ __device__ inline uint32_t rg_tile_w(const RgKernelArgs &a) { return 1u << a.tile_wlog; }
@@ -291,6 +301,17 @@ __host__ __device__ inline unsigned long long rg_tile_count(const RgKernelArgs &
 #endif
 #ifndef RG_LB_ONE
 #define RG_LB_ONE 1               // light scenes with one light (or none) run a batch of one
+#endif
+// The PLAIN light kernels' shadow mask volume (rg_shadow_vol.h; 0: every body is tested and
+// no volume is built, for A/B builds), and its two parts: the spheres' bits and the planes' bits.
+#ifndef RG_PLAIN_SHVOL
+#define RG_PLAIN_SHVOL 1
+#endif
+#ifndef RG_PLAIN_SHVOL_SPHERES
+#define RG_PLAIN_SHVOL_SPHERES 1
+#endif
+#ifndef RG_PLAIN_SHVOL_PLANES
+#define RG_PLAIN_SHVOL_PLANES 1
 #endif
 #ifndef RG_HEAVY_WPS
 #define RG_HEAVY_WPS 3            // heavy path: waves per SIMD (block = 256 * WPS threads; 168 VGPRs)

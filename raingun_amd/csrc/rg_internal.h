@@ -41,6 +41,7 @@ struct rg_launch_ctx {
     int cur = 0;
     unsigned long long *last_counters = nullptr;  // the set of the latest launch (rg_debug_counters)
     int last_plain = 0;  // the latest launch ran a PLAIN light kernel (rg_debug_last_plain)
+    int last_shvol = 0;  // ... with the scene's shadow mask volume (rg_debug_last_shadow_volume)
     unsigned long long *sticky = nullptr;    // first error of any launch since rg_stream_status cleared it
     uint32_t *tile_cost = nullptr, *tile_perm = nullptr;  // probe/sort scratch (rg_launch_tile_order), order
     size_t tile_cap = 0;
@@ -152,6 +153,7 @@ struct rg_host_tables {
     std::vector<RgBvhNode> nodes;
     std::vector<RgLightBufDev> lbuf;           // per light (kind RG_LB_NONE: no buffer), first RG_LB_MAX_LIGHTS lights
     std::vector<uint32_t> lb_start, lb_ent;    // every light's cell starts / list entries, concatenated
+    std::vector<uint32_t> shvol;               // the shadow mask volume's words (rg_shadow_vol.h), empty: none
     std::vector<uint32_t> tex_w, tex_h;
     std::vector<std::vector<uint32_t>> texels;
 };
@@ -191,6 +193,10 @@ struct rg_scene {
     int32_t lb_cam = -1;            // the camera buffer's index in lbuf (primary rays), -1: none
     int32_t n_lbdesc = 0;           // descriptors in lbuf (light slots + the camera buffer)
     bool lbuf_enabled = true;       // rg_debug_set_lightbuf
+    uint32_t *shvol = nullptr;      // shadow mask volume of the PLAIN light kernels (rg_shadow_vol.cpp), null: none
+    bool shvol_enabled = true;      // rg_debug_set_shadow_volume
+    rg_shadow_volume_info shvol_info{};  // g, bytes, build time, set share; inv / off below (rg_shvol_cell's constants)
+    float shvol_inv = 0.0f, shvol_off = 0.0f;
     bool exact_div = true;          // rg_debug_set_exact_div: 0 = launches behave as if the quotient sweep had failed
     // rg_scene_set_camera: host state, read when a launch is enqueued and passed by value in its kernel
     // arguments (RgKernelArgs::camera ..), so launches in flight keep the camera they were enqueued with

@@ -7,6 +7,7 @@
 #include "rg_k_bvh.h"
 #include "rg_k_intersect.h"
 #include "rg_k_math.h"
+#include "rg_shadow_vol_cell.h"
 
 #pragma clang fp contract(off)
 
@@ -203,6 +204,7 @@ __device__ __forceinline__ bool ray_exotic(V3 o, V3 d) {
 #ifndef RG_SHADOW_GROUP
 #define RG_SHADOW_GROUP 2  // spheres per miss-test group in the shadow pass
 #endif
+// (RG_PLAIN_SHVOL and its two parts, the PLAIN kernels' shadow mask volume: rg_device.h)
 
 template <int LB>
 struct ShadowBatch {
@@ -210,11 +212,95 @@ struct ShadowBatch {
     double ld[LB];      // light.distance(hit) (lights.rs:53-58), +inf for directional
 };
 
-template <int LB, bool NODB = false, class Src>
-__device__ __forceinline__ void trace_shadow(const RgKernelArgs &a, const Src &src, V3 o, const ShadowBatch<LB> &sb,
-                                             uint32_t full, uint32_t &occl) {
+// OR of v over the 64 lanes of a wave whose lanes are all active, as a wave-uniform value: four row
+// shifts and two row broadcasts (DPP; a lane without a source ORs in 0) leave it in lane 63.
+__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1, 3
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2, 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// One miss-test group of the shadow pass: spheres idx[0 .. g) (g <= RG_SHADOW_GROUP, wave-uniform)
+// against the batch's lights; bit l of `occl` is set where sphere and light l occlude (a: the region counters).
+template <int LB, class Src>
+__device__ __forceinline__ void shadow_group([[maybe_unused]] const RgKernelArgs &a, const Src &src, V3 o, const ShadowBatch<LB> &sb,
+                                             const int (&idx)[RG_SHADOW_GROUP], int g, uint32_t &occl) {
     constexpr int G = RG_SHADOW_GROUP;
-    const int n = a.n_sph, nfull = n - n % G;
+    RG_REGION(RGR_SH_GROUP);
+    RgSph s[G];
+    double hx[G], hy[G], hz[G], hh[G], adj[G][LB], opp[G][LB];
+    bool cand[G][LB];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        if (k < g) {
+            s[k] = src.get(idx[k]);
+            hx[k] = s[k].cx - o.x; hy[k] = s[k].cy - o.y; hz[k] = s[k].cz - o.z;   // bodies.rs:92
+            hh[k] = (hx[k] * hx[k] + hy[k] * hy[k]) + hz[k] * hz[k];                // :95 (first term)
+#pragma unroll
+            for (int l = 0; l < LB; ++l) {
+                adj[k][l] = (hx[k] * sb.d[l].x + hy[k] * sb.d[l].y) + hz[k] * sb.d[l].z;   // :93
+                opp[k][l] = hh[k] - adj[k][l] * adj[k][l];                               // :95
+                cand[k][l] = !(opp[k][l] > s[k].r2) && !((occl >> l) & 1u);              // :99
+                any |= cand[k][l];
+            }
+        }
+    }
+    if (any) {
+        RG_REGION(RGR_SH_TAIL);
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+#pragma unroll
+            for (int l = 0; l < LB; ++l) {
+                double t;
+#ifdef RG_REGION_STATS
+                if (k < g && cand[k][l]) RG_REGION(RGR_SH_PAIR);
+#endif
+                if (k < g && cand[k][l] && sphere_tail(s[k].r2, opp[k][l], adj[k][l], t) && !(t > sb.ld[l]))
+                    occl |= 1u << l;
+            }
+        }
+    }
+}
+
+// SHV (the PLAIN kernels with RG_PLAIN_SHVOL): the wave's shadow mask (rg_shadow_vol.h), wave-uniform
+// -- bit i of `smask` clear: no lane's ray can be occluded by sphere i, bit j of `pmask`: by plane j
+// (bodies past the masks' bits are always tested; all ones without a volume).  The walk takes its
+// groups from the set bits.  `occl` is an OR of hits and a skipped body has none, so the result is the
+// full scan's in any order.
+template <int LB, bool NODB = false, bool SHV = false, class Src>
+__device__ __forceinline__ void trace_shadow(const RgKernelArgs &a, const Src &src, V3 o, const ShadowBatch<LB> &sb,
+                                             uint32_t full, uint32_t &occl, [[maybe_unused]] uint32_t smask = ~0u,
+                                             [[maybe_unused]] uint32_t pmask = ~0u) {
+    constexpr int G = RG_SHADOW_GROUP;
+    const int n = a.n_sph;
+    if constexpr (SHV && RG_PLAIN_SHVOL_SPHERES != 0) {
+        for (int base = 0; base < n; base += 32) {  // 32 spheres per pass: the first pass's under the mask
+            const uint32_t lim = n - base >= 32 ? ~0u : (1u << (n - base)) - 1u;
+            uint32_t left = base == 0 ? smask & lim : lim;
+            for (int ng = 1; left != 0u; ++ng) {
+                int idx[G], g = 0;
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    idx[k] = 0;
+                    if (left != 0u) {
+                        idx[k] = base + __builtin_ctz(left);
+                        left &= left - 1u;
+                        g = k + 1;
+                    }
+                }
+                shadow_group<LB>(a, src, o, sb, idx, g, occl);
+                if ((ng & 3) == 0 && !__any(occl != full)) return;
+            }
+        }
+    } else {
+    // (shadow_group's body, kept as it stood: routed through the helper, the kernels without the
+    // mask compiled to other code than their parent's -- profiles/shvol/kernel_isa_diff.txt)
+    const int nfull = n - n % G;
     for (int i = 0; i < n;) {
         const int g = i < nfull ? G : 1;  // wave-uniform
         RG_REGION(RGR_SH_GROUP);
@@ -255,8 +341,12 @@ __device__ __forceinline__ void trace_shadow(const RgKernelArgs &a, const Src &s
         i += g;
         if ((i & 7) == 0 && !__any(occl != full)) return;
     }
+    }
     if (!__any(occl != full)) return;
     for (int i = 0; i < a.n_pln; ++i) {
+        if constexpr (SHV && RG_PLAIN_SHVOL_PLANES != 0) {
+            if (i < RG_SHVOL_MAX_BODIES && !((pmask >> i) & 1u)) continue;  // (wave-uniform)
+        }
         const RgPln p = src.getp(i);
         const double vx = p.ox - o.x, vy = p.oy - o.y, vz = p.oz - o.z;     // bodies.rs:139
         const double num = (vx * p.nx + vy * p.ny) + vz * p.nz;             // :140 numerator

@@ -235,6 +235,7 @@ rg_status launch_and_snapshot(const rg_launch_desc &d, rg_launch_ctx *cx, RgKern
     a.snap_out = snap_dev;
     if (a.out_rows > 0) {
         if (!ok(rg_launch_render(&a, disp, st, &cx->last_plain))) return RG_ERR_DEVICE;
+        cx->last_shvol = cx->last_plain && a.shvol != nullptr;  // only the PLAIN kernels read it
         cx->cur = 1 - cx->cur;  // the kernel zeroes the other set for the next launch
     }
     if (d.timed && !ok(hipEventRecord(cx->ev1, st))) return RG_ERR_DEVICE;

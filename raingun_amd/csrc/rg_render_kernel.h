@@ -37,6 +37,7 @@
 #include "rg_k_shade.h"
 #include "rg_k_trace.h"
 #include "rg_render_cfg.h"
+#include "rg_shadow_vol_cell.h"
 
 #pragma clang fp contract(off)
 
@@ -101,6 +102,9 @@ void rg_render_kernel(RgKernelArgs a) {
     // PLAIN: the spherical lights' sqrt and 1.0 / m without their range scaling, per lane admitted
     // (rg_k_math.h sqrt_rcp_guarded)
     constexpr bool UL = PLAIN && RG_PLAIN_ULIGHT != 0;
+    // PLAIN: a shaded hit looks up its shadow origin's word of the scene's shadow mask volume, the wave
+    // ORs the words and trace_shadow walks the bodies left (rg_shadow_vol.h)
+    constexpr bool SHV = PLAIN && RG_PLAIN_SHVOL != 0;
 #ifdef RG_WAVE_TIMES  // diagnostic: per-wave start (before staging), staged, end (100 MHz ticks), tiles
     const unsigned long long t_wave0 = wall_clock64();
     uint32_t wt_tiles = 0;
@@ -288,6 +292,7 @@ void rg_render_kernel(RgKernelArgs a) {
     Ray q;                 // current query (shadow: q.o = shared origin)
     ShadowBatch<LB> sb;        // shadow: the batch's directions and light distances
     uint32_t occl_full = 0u;
+    [[maybe_unused]] uint32_t shw = 0u;  // SHV: the batch's word of the shadow mask volume (set with the batch)
     int qdepth = 0;        // closest: depth of the ray
     // hit being shaded
     V3 hp = v3(0, 0, 0), hn = v3(0, 0, 0);
@@ -383,6 +388,17 @@ void rg_render_kernel(RgKernelArgs a) {
                             // by the shadow pass) carries the reflection direction until the
                             // batch is shaded -- the frame holds only colour state
                             q.o = add(h, scl(n, SHADOW_BIAS));
+                            if constexpr (SHV) {
+                                // the origin's word of the shadow mask volume: one load, behind the texel's,
+                                // read when the wave forms its mask (an origin without a cell: every body)
+                                shw = RG_SHVOL_ALL;
+                                if (a.shvol) {  // (wave-uniform)
+                                    const int cell = rg_shvol_cell((float)q.o.x, (float)q.o.y, (float)q.o.z, a.shvol_inv,
+                                                                   a.shvol_off, (int)a.shvol_g);
+                                    const uint32_t w = a.shvol[cell >= 0 ? cell : 0];
+                                    if (cell >= 0) shw = w;
+                                }
+                            }
                             // (rendering.rs:88: its frame is pushed once the batch is shaded)
                             if (kind == 2) q.d = sub(q.d, scl(n, 2.0 * dot(q.d, n)));  // ray.rs:58
                             occl_full = 0u;
@@ -1011,10 +1027,20 @@ void rg_render_kernel(RgKernelArgs a) {
                     }
                 }
             }
+            // SHV: the wave's shadow mask -- the volume's words of the lanes about to trace a batch (each
+            // set up in this iteration), ORed into one wave-uniform value (every lane is active here)
+            [[maybe_unused]] uint32_t smask = ~0u, pmask = ~0u;
+            if constexpr (SHV) {
+                if (a.shvol) {  // (wave-uniform; spheres at bits 0..15, planes at 16..31)
+                    const uint32_t wm = wave_or(mode == MODE_SHADOW && !exact ? shw : 0u);
+                    smask = wm & 0xFFFFu;
+                    pmask = wm >> 16;
+                }
+            }
             if (mode == MODE_SHADOW && !exact) {
                 RG_REGION(RGR_Q_SHADOW);
                 occl = ~occl_full & ((1u << LB) - 1u);  // absent slots count as done
-                trace_shadow<LB, PLAIN>(a, src, q.o, sb, (1u << LB) - 1u, occl);
+                trace_shadow<LB, PLAIN, SHV>(a, src, q.o, sb, (1u << LB) - 1u, occl, smask, pmask);
             }
         }
 #ifdef RG_TILE_TIMES

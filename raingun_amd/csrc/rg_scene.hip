@@ -19,6 +19,7 @@
 #include "rg_device.h"
 #include "rg_exact.h"
 #include "rg_lightbuf.h"
+#include "rg_shadow_vol.h"
 #include "rg_internal.h"
 
 #pragma clang fp contract(off)
@@ -117,6 +118,7 @@ rg_status upload_tables(rg_scene *s, const rg_host_tables &h) {
     RG_UP(lbuf, lbuf);
     RG_UP(lb_start, lb_start);
     RG_UP(lb_ent, lb_ent);
+    RG_UP(shvol, shvol);
 #undef RG_UP
     // textures: RGBA8 -> one u32 per texel (one 4-byte gather per lookup)
     std::vector<RgTexDev> texs(h.tex_w.size());
@@ -156,6 +158,9 @@ void copy_scalars(rg_scene *dst, const rg_scene *src) {
     dst->bvh_margin = src->bvh_margin;
     dst->bvh_extent = src->bvh_extent;
     dst->bvh_info = src->bvh_info;
+    dst->shvol_info = src->shvol_info;
+    dst->shvol_inv = src->shvol_inv;
+    dst->shvol_off = src->shvol_off;
 }
 
 }  // namespace
@@ -238,6 +243,12 @@ RgKernelArgs rg_make_args(const rg_scene *s) {
     a.max_depth = s->max_depth;
     a.fov_adjustment = fov_adjustment(s->fov);
     a.tile_wlog = 3;  // 8x8 tiles
+    // the shadow mask volume (PLAIN light kernels; rg_debug_set_shadow_volume(0): none)
+    const bool shvol = RG_PLAIN_SHVOL != 0 && s->shvol_enabled && s->shvol != nullptr;
+    a.shvol = shvol ? s->shvol : nullptr;
+    a.shvol_g = shvol ? (uint32_t)s->shvol_info.g : 0u;
+    a.shvol_inv = s->shvol_inv;
+    a.shvol_off = s->shvol_off;
     return a;
 }
 
@@ -332,6 +343,7 @@ void rg_sync_settings(rg_scene *dst, const rg_scene *src) {
     dst->path = src->path;
     dst->bvh_enabled = src->bvh_enabled;
     dst->lbuf_enabled = src->lbuf_enabled;
+    dst->shvol_enabled = src->shvol_enabled;
     dst->exact_div = src->exact_div;
     dst->has_camera = src->has_camera;
     dst->camera = src->camera;
@@ -529,6 +541,37 @@ rg_status rg_scene_create(const rg_scene_desc *d, int32_t device, rg_scene **out
         s->n_lbdesc = (int32_t)h.lbuf.size();
         s->bvh_info.lbuf_bytes = (int64_t)((h.lb_ent.size() + h.lb_start.size()) * sizeof(uint32_t) +
                                            h.lbuf.size() * sizeof(RgLightBufDev));
+    }
+    // Shadow mask volume (rg_shadow_vol.cpp) over the sphere and plane tables in kernel order: scenes
+    // the PLAIN light kernels can run (no disks, no boxes)
+    if (RG_PLAIN_SHVOL != 0 && h.dsk.empty() && h.box.empty() && !nan_scene) {
+        std::vector<double> sp(sph_raw);  // centre, radius by table position (a BVH reorders the tables)
+        for (size_t j = 0; !h.nodes.empty() && j < h.sph.size(); ++j)
+            std::memcpy(&sp[4 * j], &sph_raw[4 * (size_t)bvh.order[j]], 4 * sizeof(double));
+        std::vector<double> pl(6 * h.pln.size());
+        for (size_t j = 0; j < h.pln.size(); ++j) {
+            const RgPln &p = h.pln[j];
+            const double v[6] = {p.ox, p.oy, p.oz, p.nx, p.ny, p.nz};
+            std::memcpy(&pl[6 * j], v, sizeof v);
+        }
+        std::vector<RgShadowVolLight> ls(h.lights.size());
+        for (size_t l = 0; l < ls.size(); ++l) {
+            ls[l].kind = h.lights[l].kind;
+            std::memcpy(ls[l].v, h.lights[l].v, sizeof ls[l].v);
+            std::memcpy(ls[l].dn, h.lights[l].dn, sizeof ls[l].dn);
+        }
+        RgShadowVolBuild sv;
+        if (rg_build_shadow_vol(sp.data(), (int)h.sph.size(), pl.data(), (int)h.pln.size(), ls.data(), (int)ls.size(),
+                                RG_SHVOL_G, sv)) {
+            s->shvol_info.built = 1;
+            s->shvol_info.g = sv.g;
+            s->shvol_info.bytes = (int64_t)(sv.words.size() * sizeof(uint32_t));
+            s->shvol_info.build_ms = sv.build_ms;
+            s->shvol_info.set_share = sv.set_share;
+            s->shvol_inv = sv.inv;
+            s->shvol_off = sv.off;
+            h.shvol = std::move(sv.words);
+        }
     }
     h.tex_w.resize(d->n_textures);
     h.tex_h.resize(d->n_textures);

@@ -321,6 +321,24 @@ class DeviceScene:
         _abi.check(_abi.lib().rg_debug_last_plain(self.handle, C.byref(plain)))
         return plain.value == 1
 
+    def set_shadow_volume(self, on: bool) -> None:
+        """False: launches pass no shadow mask volume, so the PLAIN light kernels test every body
+        (include/raingun_debug.h rg_debug_set_shadow_volume)."""
+        _abi.check(_abi.lib().rg_debug_set_shadow_volume(self.handle, 1 if on else 0))
+
+    def shadow_volume_info(self) -> dict:
+        """rg_debug_shadow_volume_info: built, enabled, g, bytes, build_ms, set_share."""
+        info = _abi.rg_shadow_volume_info()
+        _abi.check(_abi.lib().rg_debug_shadow_volume_info(self.handle, C.byref(info)))
+        return {"built": bool(info.built), "enabled": bool(info.enabled), "g": info.g, "bytes": info.bytes,
+                "build_ms": info.build_ms, "set_share": info.set_share}
+
+    def last_shadow_volume(self) -> bool:
+        """Did the latest render launch run a PLAIN light kernel with the shadow mask volume?"""
+        used = C.c_int32(-1)
+        _abi.check(_abi.lib().rg_debug_last_shadow_volume(self.handle, C.byref(used)))
+        return used.value == 1
+
     def set_exact_div(self, enable: bool) -> None:
         """False: launches behave as if the PLAIN kernels' camera-quotient check had failed, so they run
         the general kernel (include/raingun_debug.h rg_debug_set_exact_div)."""
