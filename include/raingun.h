@@ -412,6 +412,47 @@ rg_status rg_render_aov_async(const rg_scene *scene, uint32_t width, uint32_t he
 rg_status rg_render_multi(const rg_scene *scene, uint32_t width, uint32_t height, int32_t ngpus,
                           uint32_t tile_rows, uint8_t *rgba_out, rg_stats *stats);
 
+/* A thin lens: depth of field for the supersampled frames.  aperture: the lens radius in world units;
+ * focus: the distance of the plane in focus along the camera's forward, in units of |forward|.
+ * It applies to the samples x samples rays per pixel of rg_render_image_aa and rg_render_aa_async for
+ * samples >= 2, and to nothing else: with samples == 1, without a lens or with aperture == 0 those two
+ * calls launch the kernels and give the bytes they give today.  Deterministic, no random numbers: with
+ * (E, R, U, F) the scene's camera (or {0, (1,0,0), (0,1,0), (0,0,-1)} without one), k = samples and sx, sy
+ * the sensor coordinates of pixel (X, Y) of the kW x kH sample frame -- f64, unfused, in this order:
+ *   D.c = (R.c * sx + U.c * sy) + F.c
+ *   s = (Y % k) * k + (X % k);  (pu, pv) = points_k[s]           the sample's point of the unit disk
+ *   n = (Y / k) * W + (X / k);  h = lowbias32(n)                 the output pixel's hash (u32):
+ *         n ^= n >> 16; n *= 0x7feb352d; n ^= n >> 15; n *= 0x846ca68b; n ^= n >> 16
+ *   (c, g) = rotations[h & 63]                                   that pixel's turn of the lens disk
+ *   qu = c * pu - g * pv;  qv = g * pu + c * pv
+ *   O.c = LR.c * qu + LU.c * qv           LR = normalize(R) * aperture, LU = normalize(U) * aperture
+ *   ray = Ray::new(E + O, normalize(D * focus - O))              a primary ray at depth 0
+ * points_k and rotations are rg_lens_tables'.  Every sample of a pixel meets the plane in focus where the
+ * pinhole ray of its sub-pixel does; the per-pixel turn keeps an out-of-focus object from showing as k^2
+ * ghost copies. */
+typedef struct rg_lens { double aperture, focus; } rg_lens;
+
+/* The lens of every later rg_render_image_aa / rg_render_aa_async of `scene`; NULL or aperture == 0: the
+ * pinhole again, and with it exactly the kernels those calls launched before.  Host state like the camera:
+ * read when a launch is enqueued, carried by value in the kernel's arguments (launches in flight keep
+ * theirs; the tables on the device are made once per scene and never rewritten), and followed by
+ * rg_render_multi's replicas.  The entry points that trace one ray per pixel ignore it: rg_render_image,
+ * rg_render_tiles / _async / _pipelined, rg_render_stream, rg_render_multi, rg_frames_*, rg_render_aov /
+ * _async and rg_trace.  While a lens with aperture > 0 is set, rg_render_image_aa_adaptive and
+ * rg_render_aa_adaptive return RG_ERR_INVALID_ARGUMENT: their edge mask comes from a pinhole frame and
+ * says nothing about defocus.  Ray counts, error_pixel and status codes of the two AA calls keep their
+ * meaning; while the scene's camera has a zero right or up (no axis to span the lens disk with) they
+ * return RG_ERR_INVALID_ARGUMENT for samples >= 2.  RG_ERR_INVALID_ARGUMENT for a null scene, a non-finite
+ * member, aperture < 0 or focus <= 0 (the scene keeps the lens it had). */
+rg_status rg_scene_set_lens(rg_scene *scene, const rg_lens *lens);
+
+/* The lens's two tables, pure host code.  points: 2 * samples^2 doubles, the concentric (Shirley-Chiu) map
+ * onto the unit disk of the cell centres ((i + 0.5) / samples, (j + 0.5) / samples) at index j * samples + i
+ * (samples == 1 and the centre cell of an odd samples: exactly (0, 0)).  rotations (nullable): 128 doubles,
+ * (cos, sin) of 2 pi m / 64 for m = 0 .. 63.  RG_ERR_INVALID_ARGUMENT for samples outside 1 .. 8 or a null
+ * `points`. */
+rg_status rg_lens_tables(uint32_t samples, double *points, double *rotations);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,10 @@ class rg_aov(C.Structure):  # device or host pointers, each nullable (include/ra
                 ("albedo", C.c_void_p)]
 
 
+class rg_lens(C.Structure):
+    _fields_ = [("aperture", C.c_double), ("focus", C.c_double)]
+
+
 class rg_bvh_info(C.Structure):  # include/raingun_debug.h
     _fields_ = [("built", C.c_int32), ("enabled", C.c_int32), ("nodes", C.c_int32), ("leaves", C.c_int32),
                 ("depth", C.c_int32), ("margin", C.c_float), ("origin_bound", C.c_float), ("lane_stack", C.c_int32),
@@ -162,6 +166,8 @@ EXPORTED_SYMBOLS = (
     "rg_scene_set_camera",
     "rg_render_aov",
     "rg_render_aov_async",
+    "rg_scene_set_lens",
+    "rg_lens_tables",
 )
 # include/raingun_debug.h
 DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "rg_debug_counters",
@@ -207,6 +213,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.rg_camera_look_at.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), P(rg_camera)]
     lib.rg_scene_set_camera.restype = C.c_int32
     lib.rg_scene_set_camera.argtypes = [C.c_void_p, P(rg_camera)]
+    lib.rg_scene_set_lens.restype = C.c_int32
+    lib.rg_scene_set_lens.argtypes = [C.c_void_p, P(rg_lens)]
+    lib.rg_lens_tables.restype = C.c_int32
+    lib.rg_lens_tables.argtypes = [C.c_uint32, P(C.c_double), P(C.c_double)]
     lib.rg_render_image.restype = C.c_int32
     lib.rg_render_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, P(rg_stats)]
     lib.rg_render_tiles_async.restype = C.c_int32

@@ -1,4 +1,5 @@
-"""The movable camera (include/raingun.h rg_camera; raingun_amd/csrc/rg_camera.h states the arithmetic).
+"""The movable camera (include/raingun.h rg_camera; raingun_amd/csrc/rg_camera.h states the arithmetic),
+and the thin lens (Lens) that supersampled frames may look through.
 
 A camera is eye, right, up, forward: four triples of doubles.  The primary ray of pixel (x, y) leaves
 `eye` towards normalize((right * sx + up * sy) + forward), with sx, sy the reference's sensor
@@ -10,7 +11,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 Vec = Tuple[float, float, float]
 
@@ -81,6 +82,36 @@ class Camera:
         if not (_finite(r) and _finite(u) and _finite(f) and any(x != 0.0 for x in f)):
             raise ValueError("look_at: the result is no camera")
         return Camera(e, r, u, f)
+
+
+@dataclass(frozen=True)
+class Lens:
+    """A thin lens (include/raingun.h rg_lens; raingun_amd/csrc/rg_lens.h states the arithmetic): depth of
+    field for the supersampled frames (samples >= 2).  aperture: the lens radius in world units, 0 a
+    pinhole; focus: the distance of the plane in focus along the camera's forward, in units of |forward|."""
+    aperture: float
+    focus: float
+
+    def __post_init__(self):
+        object.__setattr__(self, "aperture", float(self.aperture))
+        object.__setattr__(self, "focus", float(self.focus))
+        if not (math.isfinite(self.aperture) and math.isfinite(self.focus) and self.aperture >= 0.0 and self.focus > 0.0):
+            raise ValueError("a lens needs a finite aperture >= 0 and a finite focus > 0")
+
+
+def lens_from_flags(aperture, focus, samples: int, adaptive) -> "Optional[Lens]":
+    """The lens of the CLI's --aperture R --focus D (each a string or None): None without either.
+    ValueError unless both are given and are a lens, with --samples >= 2 and no --adaptive."""
+    if aperture is None and focus is None:
+        return None
+    if aperture is None or focus is None:
+        raise ValueError("--aperture and --focus go together")
+    lens = Lens(float(aperture), float(focus))  # float('x') raises ValueError
+    if samples < 2:
+        raise ValueError("a lens needs --samples 2 or more")
+    if adaptive is not None:
+        raise ValueError("a lens cannot be combined with --adaptive")
+    return lens
 
 
 def parse_triple(text: str) -> Vec:

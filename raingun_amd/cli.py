@@ -1,7 +1,8 @@
 """`raingun` command line, mirroring the reference's src/main.rs + src/render.rs.
 
     python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
-                              [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aov LAYERS] [-o FILE] FILE
+                              [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D]
+                              [--aov LAYERS] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
@@ -18,6 +19,11 @@ the reference, whose view is from the origin down -z) move the camera
 (rg_scene_set_camera): --up defaults to 0,1,0, --eye without --look-at looks
 down -z from the eye; a malformed triple or a rejected look-at ends the run
 like any other bad flag value.  The scene file has no camera key.
+`--aperture R --focus D` (not in the reference) put a thin lens of radius R in
+front of the camera, focused on the plane D forward lengths away
+(rg_scene_set_lens): depth of field from the N x N rays of --samples, so they
+need --samples 2 or more and refuse --adaptive, and go together; they combine
+with the camera and the size flags.
 `--aov LAYERS` (not in the reference; a comma list of body, depth, normal, uv,
 albedo, or `all`) also writes, next to `-o out.png`, `out.<layer>.png` for each
 named layer: what lies under each pixel (rg_render_aov), as the pictures of
@@ -41,7 +47,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import aov
-from .camera import Camera, camera_from_flags, parse_triple
+from .camera import Camera, Lens, camera_from_flags, lens_from_flags, parse_triple
 
 
 @dataclass
@@ -52,6 +58,7 @@ class RenderOptions:          # render.rs:32-46
     samples: int = 1          # N x N rays per pixel (--samples; not in the reference)
     adaptive: Optional[int] = None  # contrast threshold of adaptive anti-aliasing (--adaptive)
     camera: Optional[Camera] = None  # --eye / --look-at / --up (not in the reference)
+    lens: Optional[Lens] = None      # --aperture / --focus (not in the reference)
     aov: tuple = ()           # layers of --aov, in aov.LAYERS order (not in the reference)
 
 
@@ -88,6 +95,8 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("--look-at", dest="look_at", metavar="X,Y,Z",
                    help="Point the camera looks at (default: straight down -z from the eye).")
     p.add_argument("--up", metavar="X,Y,Z", help="Up hint of --look-at (default 0,1,0).")
+    p.add_argument("--aperture", metavar="R", help="Lens radius in world units (with --focus and --samples >= 2).")
+    p.add_argument("--focus", metavar="D", help="Distance of the plane in focus, in lengths of the forward vector.")
     p.add_argument("--aov", metavar="LAYERS",
                    help="Also write FILENAME.<layer>.png for each of a comma list of body, depth, normal, uv, "
                         "albedo (or all).")
@@ -106,6 +115,10 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
         if not 0 <= o.adaptive <= 256:
             raise SystemExit("adaptive must be between 0 and 256")
     o.camera = _parse_camera(ns)
+    try:
+        o.lens = lens_from_flags(ns.aperture, ns.focus, o.samples, o.adaptive)
+    except ValueError as e:
+        raise SystemExit(f"Could not build the lens: {e}") from None
     if ns.aov is not None:
         try:
             o.aov = aov.parse_layers(ns.aov)
@@ -215,6 +228,7 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
 
     ds = DeviceScene(scene, device=ns.gpu)
     ds.set_camera(opts.camera)
+    ds.set_lens(opts.lens)
     t0 = time.perf_counter()                     # render.rs:54-56
     if opts.samples > 1 and opts.adaptive is not None:
         img = ds.render_image_aa_adaptive(opts.width, opts.height, opts.samples, opts.adaptive)

@@ -26,6 +26,7 @@
 #include "rg_device.h"
 #include "rg_internal.h"
 #include "rg_launchers.h"
+#include "rg_lens.h"
 #include "rg_sample_tiles.h"
 
 #pragma clang fp contract(off)
@@ -40,6 +41,7 @@ void rg_aa_res_release(rg_aa_res &r) {
     if (r.d_list) (void)hipFree(r.d_list);
     if (r.d_counts) (void)hipFree(r.d_counts);
     if (r.h_counts) (void)hipHostFree(r.h_counts);
+    if (r.d_lens) (void)hipFree(r.d_lens);
     for (int i = 0; i < 2; ++i) {
         if (r.slot_rgba[i]) (void)hipFree(r.slot_rgba[i]);
         if (r.slot_rgb[i]) (void)hipFree(r.slot_rgb[i]);
@@ -80,6 +82,22 @@ rg_status ensure_aa_res(const rg_scene *s, const aa_plan &p) {
         if ((st = rg_grow(RG_MEM_DEVICE, r.slot_cap[i], samples,
                           {{r.slot_rgba[i], samples * 4 + 16}, {r.slot_rgb[i], samples * 12 + 16}})) != RG_OK)
             return st;
+    // a frame through the scene's lens: the tables, once per scene (a blocking copy: they are complete
+    // before the first launch that reads them is enqueued, and nothing writes them again)
+    if (rg_lens_active(s->lens.aperture, p.k) && !r.d_lens) {
+        double table[RG_LENS_TABLE_DOUBLES];
+        rg_lens_make_tables(table);
+        void *d = nullptr;
+        if (!ok(hipMalloc(&d, sizeof table))) {
+            (void)hipGetLastError();
+            return RG_ERR_OUT_OF_MEMORY;
+        }
+        if (!ok(hipMemcpy(d, table, sizeof table, hipMemcpyHostToDevice))) {
+            (void)hipFree(d);
+            return RG_ERR_DEVICE;
+        }
+        r.d_lens = static_cast<double *>(d);
+    }
     return RG_OK;
 }
 
@@ -98,6 +116,8 @@ rg_status enqueue_bands(const rg_scene *s, const aa_plan &p, uint8_t *out_rgba, 
         d.rgb = static_cast<float *>(r.slot_rgb[i]);
         d.stream = rs;
         d.snap = snaps ? r.h_snap + 4 * (size_t)b : nullptr;
+        d.lens_k = p.k;  // the samples of a pixel leave the scene's lens, if it has one (k >= 2)
+        d.lens_tab = r.d_lens;
         const rg_status st = rg_launch_tiles(s, d);
         if (st != RG_OK) return st;
         const size_t off = (size_t)b * p.band_rows * p.width;  // the last band is partial: only rows below host_rows
@@ -291,6 +311,8 @@ rg_status adaptive_stats(const rg_scene *s, const aa_plan &p, rg_stats *stats) {
 rg_status adaptive_check(const void *scene, uint32_t W, uint32_t H, uint32_t k, uint32_t threshold, const void *rgba) {
     const rg_status v = aa_validate(scene, W, H, k, rgba);
     if (v != RG_OK) return v;
+    // no adaptive form through a lens: the edge mask comes from a pinhole frame and says nothing about defocus
+    if (static_cast<const rg_scene *>(scene)->lens.aperture > 0.0) return RG_ERR_INVALID_ARGUMENT;
     return threshold > 256 ? RG_ERR_INVALID_ARGUMENT : RG_OK;
 }
 

@@ -256,6 +256,18 @@ struct RgKernelArgs {
     // the struct grows by 32 bytes, so the arguments that follow it in other kernels (rg_trace_kernel,
     // rg_aov_kernel) keep their 16-byte phase and those kernels their code (profiles/shvol/kernel_isa_diff.txt)
     uint32_t shvol_pad[3];
+    // The launch's thin lens (rg_lens.h; rg_scene_set_lens), by value: lens != 0 selects the lens family
+    // of rg_render_kernel (rg_render_cfg.h RG_MAXD_LENS; a band of a supersampled frame with lens_k x lens_k
+    // samples per pixel, rg_aa.hip), whose primary rays leave cam_eye + O for the point of the plane in
+    // focus: lens_r / lens_u are normalize(cam_right / cam_up) * aperture, lens_tab the scene's device
+    // table (RG_LENS_TABLE_DOUBLES doubles: every k's points, then the rotations).  Such a launch always
+    // has camera != 0 (the identity camera where the scene has none).  0: the other members are not read.
+    // At the end of the struct: the other instantiations keep their argument offsets; it grows by 80
+    // bytes, a multiple of 16, for the reason shvol_pad gives.
+    uint32_t lens, lens_k;
+    double lens_focus, lens_r[3], lens_u[3];
+    const double *lens_tab;
+    uint32_t lens_pad[2];
 };
 
 __host__ __device__ inline uint32_t rg_tile_w(const RgKernelArgs &a) { return 1u << a.tile_wlog; }

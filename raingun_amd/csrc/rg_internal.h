@@ -134,6 +134,9 @@ struct rg_aa_res : rg_band_res {
     size_t n_marks = 0;
     float pass_ms[5] = {0, 0, 0, 0, 0};
     uint32_t flagged = 0, listed_tiles = 0, bands_launched = 0;
+    // the thin lens's tables on the device (rg_lens.h RG_LENS_TABLE_DOUBLES doubles): made on the first frame
+    // through a lens, never rewritten, so launches in flight may read them whatever the scene is given next
+    double *d_lens = nullptr;
 };
 
 // Everything rg_scene_create uploads, as host tables (kept for replicas on
@@ -202,6 +205,9 @@ struct rg_scene {
     // arguments (RgKernelArgs::camera ..), so launches in flight keep the camera they were enqueued with
     bool has_camera = false;
     rg_camera camera{};
+    // rg_scene_set_lens: host state like the camera, read when a band of a supersampled frame is enqueued
+    // and passed by value (RgKernelArgs::lens ..); aperture == 0: no lens
+    rg_lens lens{0.0, 1.0};
     float bvh_obound = 0.0f;
     double bvh_rbound = 0.0, bvh_margin = 0.0, bvh_extent = 0.0;
     rg_bvh_info bvh_info{};
@@ -277,6 +283,11 @@ struct rg_launch_desc {
     uint32_t tile_limit = 0;
     const uint8_t *px_mask = nullptr;
     uint32_t px_k = 1, px_w = 0;
+    // >= 2: a band of a supersampled frame with lens_k x lens_k samples per pixel, which sees the scene's
+    // lens if it has one (rg_lens.h rg_lens_active; dense device-resident launches only); lens_tab: the
+    // device tables (rg_aa_res::d_lens)
+    uint32_t lens_k = 0;
+    const double *lens_tab = nullptr;
 };
 
 // Enqueue one tiled render on d.stream (the body of rg_render_tiles_async).

@@ -20,6 +20,7 @@
 #include "rg_exact.h"
 #include "rg_internal.h"
 #include "rg_launchers.h"
+#include "rg_lens.h"
 
 #pragma clang fp contract(off)
 
@@ -45,6 +46,16 @@ rg_status validate(const rg_scene *s, const rg_launch_desc &d, uint32_t *out_row
                       d.tile_flags || d.cancel))
         return RG_ERR_INVALID_ARGUMENT;
     if (!s || !d.rgba || d.width == 0 || d.height == 0 || !rg_tiling_valid(&d.tiling)) return RG_ERR_INVALID_ARGUMENT;
+    if (d.lens_k && (d.px_mask || d.host_frame || d.tile_wlog != 3 || d.lens_k > RG_LENS_MAX_SAMPLES ||
+                     d.width % d.lens_k != 0 || (rg_lens_active(s->lens.aperture, d.lens_k) && !d.lens_tab)))
+        return RG_ERR_INVALID_ARGUMENT;
+    if (rg_lens_active(s->lens.aperture, d.lens_k) && s->has_camera) {
+        // the lens disk's axes are the camera's right and up, normalized: a zero (or overflowing) one spans no disk
+        double lr[3], lu[3];
+        rg_lens_axis(s->camera.right, s->lens.aperture, lr);
+        rg_lens_axis(s->camera.up, s->lens.aperture, lu);
+        if (!rg_camera_finite3(lr) || !rg_camera_finite3(lu)) return RG_ERR_INVALID_ARGUMENT;
+    }
     if (d.tile_group < 1 ||
         d.tiling.tile_offset + d.tile_group > d.tiling.tile_stride + (d.tile_group == 1 ? 1u : 0u))
         return RG_ERR_INVALID_ARGUMENT;
@@ -95,6 +106,20 @@ RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx
             a.cam_forward[k] = s->camera.forward[k];
         }
         a.plain_veto |= 4u;  // the PLAIN kernels' camera ray is the reference's view
+    }
+    if (rg_lens_active(s->lens.aperture, d.lens_k)) {  // by value, as the camera
+        if (!a.camera) {  // the reference's view as a camera: the lens family is the camera family's
+            a.camera = 1u;
+            a.cam_right[0] = a.cam_up[1] = 1.0;
+            a.cam_forward[2] = -1.0;
+            a.plain_veto |= 4u;
+        }
+        a.lens = 1u;
+        a.lens_k = d.lens_k;
+        a.lens_focus = s->lens.focus;
+        rg_lens_axis(a.cam_right, s->lens.aperture, a.lens_r);
+        rg_lens_axis(a.cam_up, s->lens.aperture, a.lens_u);
+        a.lens_tab = d.lens_tab;
     }
     a.rgba = reinterpret_cast<uint32_t *>(d.rgba);
     a.rgb = d.rgb;

@@ -36,6 +36,7 @@
 #include "rg_k_pool.h"
 #include "rg_k_shade.h"
 #include "rg_k_trace.h"
+#include "rg_lens.h"
 #include "rg_render_cfg.h"
 #include "rg_shadow_vol_cell.h"
 
@@ -91,6 +92,8 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
 // (rg_exact.h): the camera quotients of this frame size, the camera ray's range, the blob image.
 // MAXD == RG_MAXD_CAMERA (the camera family): the MAXD == 0 kernel whose primary rays leave
 // a.cam_eye in the directions of rg_camera.h and are traced by the general closest-hit query.
+// MAXD == RG_MAXD_LENS (the lens family): that kernel again, whose primary rays are the lens
+// rays of rg_lens.h -- the one difference, at the RGR_PRIM site.
 // SPARSE (global frames only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
 // renders its pixel only where a.px_mask says so (adaptive anti-aliasing, rg_aa.hip; RgKernelArgs::px_mask).
 template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
@@ -851,8 +854,19 @@ void rg_render_kernel(RgKernelArgs a) {
                         // traces as the general closest-hit query at depth 0 that it is -- nothing of
                         // trace_primary's o = 0 (sph_cc, the planes' o.n, the camera buffer) holds for it
                         double dir[3];
+                        if constexpr (K::lens) {
+                            // ... through the launch's thin lens (rg_lens.h): this sample's point of the lens
+                            // disk, turned by the output pixel's hash, towards the plane in focus
+                            double org[3];
+                            rg_lens_ray(a.cam_eye, a.cam_right, a.cam_up, a.cam_forward, sx, sy, x, y, a.lens_k,
+                                        a.width / a.lens_k, a.lens_focus, a.lens_r, a.lens_u,
+                                        a.lens_tab + 2u * rg_lens_points_offset(a.lens_k), a.lens_tab + 2u * RG_LENS_POINTS,
+                                        org, dir);
+                            q.o = v3(org[0], org[1], org[2]);
+                        } else {
                         rg_camera_direction(a.cam_right, a.cam_up, a.cam_forward, sx, sy, dir);
                         q.o = v3(a.cam_eye[0], a.cam_eye[1], a.cam_eye[2]);
+                        }
                         q.d = v3(dir[0], dir[1], dir[2]);
                         n_prim++;
                         have_result = false;

@@ -3,7 +3,8 @@
 // launch_one, which asks the occupancy, takes the grid from rg_render_grid.h and launches.
 // launch_light<MAXD, SPARSE> / launch_heavy<MAXD, HF, SPARSE> are instantiated explicitly, one per
 // rg_render_*.hip (SPARSE: the launches of a tile list under a pixel mask, global frames only;
-// MAXD = RG_MAXD_CAMERA: the launches of a scene with a camera), so every
+// MAXD = RG_MAXD_CAMERA: the launches of a scene with a camera; MAXD = RG_MAXD_LENS: the bands of a
+// supersampled frame through a thin lens), so every
 // rg_render_kernel instantiation is emitted by exactly one translation unit (the occupancy cache
 // and the HIP runtime identify a kernel by its host address); the dispatcher (rg_kernels.hip
 // dispatch_depth) sees only the declarations below.
@@ -232,3 +233,6 @@ extern template hipError_t launch_light<RG_MAXD_CAMERA>(const RgKernelArgs *, hi
 extern template hipError_t launch_heavy<RG_MAXD_CAMERA, false>(const RgKernelArgs *, hipStream_t, size_t *);
 extern template hipError_t launch_light<RG_MAXD_CAMERA, true>(const RgKernelArgs *, hipStream_t, size_t *, int *);
 extern template hipError_t launch_heavy<RG_MAXD_CAMERA, false, true>(const RgKernelArgs *, hipStream_t, size_t *);
+// the lens family (rg_render_*_lens.hip): dense only, light and heavy
+extern template hipError_t launch_light<RG_MAXD_LENS>(const RgKernelArgs *, hipStream_t, size_t *, int *);
+extern template hipError_t launch_heavy<RG_MAXD_LENS, false>(const RgKernelArgs *, hipStream_t, size_t *);

@@ -18,6 +18,7 @@
 #include "rg_camera.h"
 #include "rg_device.h"
 #include "rg_exact.h"
+#include "rg_lens.h"
 #include "rg_lightbuf.h"
 #include "rg_shadow_vol.h"
 #include "rg_internal.h"
@@ -347,6 +348,7 @@ void rg_sync_settings(rg_scene *dst, const rg_scene *src) {
     dst->exact_div = src->exact_div;
     dst->has_camera = src->has_camera;
     dst->camera = src->camera;
+    dst->lens = src->lens;
     dst->lane_min_depth = src->lane_min_depth;
     dst->tile_order = src->tile_order;
     dst->ring_flush_small = src->ring_flush_small;
@@ -631,6 +633,24 @@ rg_status rg_scene_set_camera(rg_scene *s, const rg_camera *camera) {
     if (!rg_camera_valid(camera->eye, camera->right, camera->up, camera->forward)) return RG_ERR_INVALID_ARGUMENT;
     s->camera = *camera;
     s->has_camera = true;
+    return RG_OK;
+}
+
+rg_status rg_scene_set_lens(rg_scene *s, const rg_lens *lens) {
+    if (!s) return RG_ERR_INVALID_ARGUMENT;
+    if (!lens) {  // the pinhole again: the launches and kernels of a scene that never had a lens
+        s->lens = rg_lens{0.0, 1.0};
+        return RG_OK;
+    }
+    if (!rg_lens_valid(lens->aperture, lens->focus)) return RG_ERR_INVALID_ARGUMENT;
+    s->lens = *lens;
+    return RG_OK;
+}
+
+rg_status rg_lens_tables(uint32_t samples, double *points, double *rotations) {
+    if (samples < 1 || samples > RG_LENS_MAX_SAMPLES || !points) return RG_ERR_INVALID_ARGUMENT;
+    rg_lens_make_points(samples, points);
+    if (rotations) rg_lens_make_rotations(rotations);
     return RG_OK;
 }
 

@@ -3,7 +3,8 @@
 // the HIP renderer (libraingun_hip.so: rg_render_image).
 //
 //   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
-//           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aov LAYERS] [-o FILE] [--gpu N] FILE
+//           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D] [--aov LAYERS] [-o FILE]
+//           [--gpu N] FILE
 //
 // --aov LAYERS (not in the reference): a comma list of body, depth, normal, uv, albedo, or `all`.  Next to
 // `-o out.png` the run also writes `out.<layer>.png` for each named layer: what lies under each pixel
@@ -13,6 +14,10 @@
 // --eye / --look-at / --up (not in the reference, whose view is from the origin down -z): the camera
 // (rg_camera_look_at, rg_scene_set_camera).  --up defaults to 0,1,0; --eye without --look-at looks down
 // -z from the eye; a malformed triple or a rejected look-at is an argument error.  No camera key in the YAML.
+// --aperture R --focus D (not in the reference): a thin lens of radius R (world units) focused on the plane D
+// forward lengths away (rg_scene_set_lens): depth of field from the N x N rays of --samples.  They go
+// together, need --samples 2 or more and refuse --adaptive (argument errors otherwise), and combine with
+// the camera and the size flags.
 // --adaptive T (0..256; not in the reference): the N x N rays only for pixels whose 8-neighbourhood
 // contrast in the 1-sample frame is at least T (rg_render_image_aa_adaptive); accepted with
 // --samples 1, where it has no effect.
@@ -56,6 +61,8 @@ const char *kHelp =
     "        --eye <X,Y,Z>          Camera position (default 0,0,0).\n"
     "        --look-at <X,Y,Z>      Point the camera looks at (default: straight down -z from the eye).\n"
     "        --up <X,Y,Z>           Up hint of --look-at (default 0,1,0).\n"
+    "        --aperture <R>         Lens radius in world units (with --focus and --samples 2 or more).\n"
+    "        --focus <D>            Distance of the plane in focus, in lengths of the forward vector.\n"
     "        --aov <LAYERS>         Also write FILENAME.<layer>.png for each of body,depth,normal,uv,albedo (or all).\n"
     "        --adaptive <T>         Adaptive anti-aliasing: the N x N rays only where the 1-sample frame's contrast is at least T (0..256).\n"
     "        --gpu <N>              HIP device to render on (default 0).\n"
@@ -80,7 +87,7 @@ const char *kHelp =
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
     const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr,
-               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr;
+               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr, *aperture = nullptr, *focus = nullptr;
     int gpu = 0;
 };
 
@@ -93,6 +100,8 @@ struct RenderOptions {  // render.rs:32-46
     uint32_t max_recursion_depth = 0;
     bool has_camera = false;  // --eye / --look-at / --up
     rg_camera camera{};
+    bool has_lens = false;  // --aperture / --focus
+    rg_lens lens{0.0, 1.0};
     bool aov[5] = {false, false, false, false, false};  // --aov: body, depth, normal, uv, albedo
     bool any_aov = false;
 };
@@ -110,6 +119,13 @@ bool parse_triple(const char *s, double out[3]) {  // "X,Y,Z": three finite numb
         s = end + 1;
     }
     return true;
+}
+
+bool parse_f64(const char *s, double *out) {  // one finite number, nothing else
+    if (!s || !*s || *s == ' ' || *s == '\t') return false;
+    char *end = nullptr;
+    *out = std::strtod(s, &end);
+    return end != s && *end == '\0' && *out - *out == 0.0;
 }
 
 bool parse_u32(const char *s, uint32_t *out) {  // str::parse::<u32>
@@ -158,6 +174,8 @@ Args parse_args(int argc, char **argv) {
             else if (name == "look-at") a.look_at = take_value(i, "--look-at <X,Y,Z>", val);
             else if (name == "up") a.up = take_value(i, "--up <X,Y,Z>", val);
             else if (name == "aov") a.aov = take_value(i, "--aov <LAYERS>", val);
+            else if (name == "aperture") a.aperture = take_value(i, "--aperture <R>", val);
+            else if (name == "focus") a.focus = take_value(i, "--focus <D>", val);
             else if (val) clap_error("Found argument '" + std::string(arg) + "' which wasn't expected, or isn't valid in this context");
             else if (name == "4k") { a.uhd = true; a.hd = false; }   // overrides_with("hd")
             else if (name == "hd") { a.hd = true; a.uhd = false; }   // overrides_with("4k")
@@ -223,6 +241,16 @@ RenderOptions options_from(const Args &a) {  // main.rs:70-96
             o.camera = c;
         }
         o.has_camera = true;
+    }
+    if (a.aperture || a.focus) {
+        if (!a.aperture || !a.focus) clap_error("The arguments '--aperture <R>' and '--focus <D>' go together");
+        if (!parse_f64(a.aperture, &o.lens.aperture) || o.lens.aperture < 0.0)
+            clap_error(std::string("Invalid value for '--aperture <R>': ") + a.aperture);
+        if (!parse_f64(a.focus, &o.lens.focus) || !(o.lens.focus > 0.0))
+            clap_error(std::string("Invalid value for '--focus <D>': ") + a.focus);
+        if (o.samples < 2) clap_error("The argument '--aperture <R>' needs '--samples <N>' of 2 or more");
+        if (o.has_adaptive) clap_error("The argument '--aperture <R>' cannot be used with '--adaptive <T>'");
+        o.has_lens = true;
     }
     if (a.draft) {
         o.has_depth = true;
@@ -350,6 +378,8 @@ int main(int argc, char **argv) {
     if (st != RG_OK) panic(std::string("rg_scene_create: ") + rg_status_string(st));
     if (opts.has_camera && (st = rg_scene_set_camera(scene, &opts.camera)) != RG_OK)
         panic(std::string("rg_scene_set_camera: ") + rg_status_string(st));
+    if (opts.has_lens && (st = rg_scene_set_lens(scene, &opts.lens)) != RG_OK)
+        panic(std::string("rg_scene_set_lens: ") + rg_status_string(st));
     std::vector<uint8_t> rgba((size_t)opts.width * opts.height * 4);
 
     auto t0 = std::chrono::steady_clock::now();  // render.rs:54-56

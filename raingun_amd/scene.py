@@ -27,7 +27,7 @@ from typing import Callable, List, Optional, Sequence, Union
 import numpy as np
 
 from . import _abi, aov
-from .camera import Camera
+from .camera import Camera, Lens
 from .color import Color
 
 
@@ -250,6 +250,8 @@ class DeviceScene:
             self.set_path(path)
         if bvh is not None:
             self.set_bvh(bvh)
+        if getattr(scene, "lens", None) is not None:  # Scene.set_lens
+            self.set_lens(scene.lens)
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -387,6 +389,17 @@ class DeviceScene:
         c = _abi.rg_camera((C.c_double * 3)(*camera.eye), (C.c_double * 3)(*camera.right),
                            (C.c_double * 3)(*camera.up), (C.c_double * 3)(*camera.forward))
         _abi.check(_abi.lib().rg_scene_set_camera(self.handle, C.byref(c)), "rg_scene_set_camera")
+
+    def set_lens(self, lens: Optional[Lens]) -> None:
+        """rg_scene_set_lens: the thin lens of every later render_image_aa / render_aa_async with
+        samples >= 2 (raingun_amd/camera.py Lens); None, or an aperture of 0, is the pinhole again.
+        One-ray-per-pixel renders ignore it, the adaptive ones are refused while it is set.  Launches
+        already enqueued keep the lens they were enqueued with."""
+        if lens is None:
+            _abi.check(_abi.lib().rg_scene_set_lens(self.handle, None), "rg_scene_set_lens")
+            return
+        l = _abi.rg_lens(float(lens.aperture), float(lens.focus))
+        _abi.check(_abi.lib().rg_scene_set_lens(self.handle, C.byref(l)), "rg_scene_set_lens")
 
     def render_image(self, width: int, height: int, stats: Optional[_abi.rg_stats] = None,
                      out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -569,6 +582,12 @@ class Scene:                   # scene.rs:11-31
     lights: List[Light] = field(default_factory=list)
 
     from_yaml = staticmethod(load_scene)
+    lens = None  # set_lens: not a field of the scene file (scene.rs has no lens), so not a dataclass field
+
+    def set_lens(self, lens: Optional[Lens]) -> None:
+        """The thin lens (raingun_amd/camera.py Lens) that every DeviceScene made of this scene from now on
+        starts with, and so render_image(samples >= 2); None: the pinhole."""
+        self.lens = lens
 
     def to_device(self, device: int = 0) -> DeviceScene:
         return DeviceScene(self, device)

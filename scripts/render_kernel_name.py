@@ -4,10 +4,11 @@ compiler remarks, assembly and profiles: scripts/resources.py, scripts/isa_budge
 
     parse(name)    -> {"MAXD": 8, "LSPH": True, ...}, or None if name is no rg_render_kernel
     mangle(**p)    -> the name
-    describe(p)    -> "light", "heavy host", "light tpw=-1 plain", "heavy camera sparse", ...
+    describe(p)    -> "light", "heavy host", "light tpw=-1 plain", "heavy camera sparse", "light lens", ...
 
 MAXD: array frames per lane; 0: frames in the global buffer; MAXD_CAMERA (-1, mangled Lin1E): the same
-with the primary rays of a movable camera (the camera family).
+with the primary rays of a movable camera (the camera family); MAXD_LENS (-2, mangled Lin2E): those
+through a thin lens (the lens family).
 """
 import re
 
@@ -15,6 +16,7 @@ import re
 PARAMS = [("MAXD", True), ("LSPH", False), ("LCOLD", False), ("WPS", True), ("LBT", True), ("F32F", False),
           ("BVH", False), ("TASKS", False), ("TPW", True), ("HF", False), ("SPARSE", False), ("PLAIN", False)]
 MAXD_CAMERA = -1
+MAXD_LENS = -2
 _ARG = {True: r"Li(n?\d+)E", False: r"Lb([01])E"}
 _NAME = re.compile("^_Z16rg_render_kernelI" + "".join(_ARG[i] for _, i in PARAMS) + "Ev12RgKernelArgs$")
 
@@ -41,6 +43,8 @@ def describe(p):
         kind += " host"
     if p["MAXD"] == MAXD_CAMERA:
         kind += " camera"
+    if p["MAXD"] == MAXD_LENS:
+        kind += " lens"
     if p["SPARSE"]:
         kind += " sparse"
     if p["PLAIN"]:
