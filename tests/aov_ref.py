@@ -1,44 +1,16 @@
 """The reference for AOV layers, shared by tests/test_aov_cpu.py and tests/test_gpu_aov.py.
 
-tests/native/aov_oracle.c (the pinned oracle plus one pixel loop that stops after the primary hit) is
-built into a temporary directory with the oracle's own flags (camera_ref.oracle_flags reads them from
-oracle/Makefile) and loaded with ctypes.  Test-side only: nothing in raingun_amd/ includes or loads it.
+rga_render of tests/native/ref_frames.c (the pinned oracle plus its pixel loop stopping after the primary hit),
+through tests/ref_lib.py.  Test-side only: nothing in raingun_amd/ includes or loads it.
 """
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-import camera_ref
+import ref_lib
 from raingun_amd import _abi, aov
 from raingun_amd.scene import SceneDesc
-
-REPO = Path(__file__).resolve().parents[1]
-SRC = REPO / "tests" / "native" / "aov_oracle.c"
-
-_LIB = None
-_TMP = None
-
-
-def lib():
-    global _LIB, _TMP
-    if _LIB is None:
-        _TMP = tempfile.TemporaryDirectory(prefix="aov_oracle_")
-        out = Path(_TMP.name) / "libaov_oracle.so"
-        cc, flags = camera_ref.oracle_flags()
-        subprocess.run([cc, *flags, "-shared", "-pthread", "-o", str(out), str(SRC), "-lm"], check=True, timeout=300)
-        l = C.CDLL(str(out))
-        P = C.POINTER
-        l.rga_render.restype = C.c_int32
-        l.rga_render.argtypes = [P(_abi.rg_scene_desc), C.c_uint32, C.c_uint32, P(_abi.rg_tiling), P(_abi.rg_camera),
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(_abi.rg_ray_counts),
-                                 P(C.c_int64)]
-        l.rgo_tiling_rows.restype = C.c_uint32
-        l.rgo_tiling_rows.argtypes = [C.c_uint32, P(_abi.rg_tiling)]
-        _LIB = l
-    return _LIB
+from ref_lib import c_camera, lib
 
 
 def render(scene, width: int, height: int, cam=None, layers=aov.LAYERS, tile_rows: int = 0, stride: int = 1,
@@ -51,24 +23,16 @@ def render(scene, width: int, height: int, cam=None, layers=aov.LAYERS, tile_row
     ptr = [out[n].ctypes.data if n in out else None for n in aov.LAYERS]
     counts = _abi.rg_ray_counts()
     err = C.c_int64(-1)
-    cc = camera_ref.c_camera(cam) if cam is not None else None
+    cc = c_camera(cam) if cam is not None else None
     st = lib().rga_render(desc.ptr(), width, height, C.byref(t), C.byref(cc) if cc is not None else None, *ptr,
                           C.byref(counts), C.byref(err))
     return st, out, counts.as_dict(), int(err.value)
 
 
-_CACHE = {}
-
-
 def cached(key, scene, width, height, cam=None, **tiling):
     """render() with every layer, computed once per key and handed out read-only."""
-    k = (key, cam, width, height, tuple(sorted(tiling.items())))
-    if k not in _CACHE:
-        st, out, counts, err = render(scene, width, height, cam, **tiling)
-        for a in out.values():
-            a.setflags(write=False)
-        _CACHE[k] = (st, out, counts, err)
-    return _CACHE[k]
+    k = ("aov", key, cam, width, height, tuple(sorted(tiling.items())))
+    return ref_lib.cached(k, render, scene, width, height, cam, **tiling)
 
 
 def bits(a: np.ndarray) -> np.ndarray:

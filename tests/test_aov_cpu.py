@@ -1,5 +1,5 @@
-"""AOV layers on the CPU (no GPU needed): the AOV reference (tests/native/aov_oracle.c through
-tests/aov_ref.py) tied to the pinned oracle, aov.visualize's known answers, and the bindings.
+"""AOV layers on the CPU (no GPU needed): the AOV reference (rga_render of tests/native/ref_frames.c
+through tests/aov_ref.py) tied to the pinned oracle, aov.visualize's known answers, and the bindings.
 
 (a) `body` and `depth` of the reference equal rgo_trace on create_prime's rays, bit for bit (a miss is
     -1 / 0.0 there and -1 / +inf here), and the identity camera gives the same layers.

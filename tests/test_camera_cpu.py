@@ -2,8 +2,8 @@
 
 1. tests/native/camera_test.cpp against the shared header raingun_amd/csrc/rg_camera.h (a stand-alone
    program, AddressSanitizer + UBSan, run as a child process).
-2. The camera reference (tests/native/camera_oracle.c through tests/camera_ref.py) tied to the pinned
-   oracle: (a) with the identity camera it gives oracle.render's bytes, ray counts and status; (b) with
+2. The camera reference (rgc_render of tests/native/ref_frames.c through tests/camera_ref.py), and with
+   it the one pixel loop of that file, tied to the pinned oracle: (a) with the identity camera it gives oracle.render's bytes, ray counts and status; (b) with
    the camera turned 180 degrees about y it gives, on the scene mirrored in x and z, oracle.render's
    frame of the ORIGINAL scene -- untextured scenes only (sphere atan2 texture coordinates and the
    planes' world-axis texture frames do not turn with the scene); and the control: the turned camera
@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import camera_ref
+import ref_lib
 from raingun_amd.camera import Camera, camera_from_flags, parse_triple
 from raingun_amd.cli import parse_arguments
 from raingun_amd.scene import SceneDesc
@@ -105,14 +106,15 @@ def test_turned_camera_on_the_mirrored_scene_is_the_oracle(oracle_lib, example_s
 
 
 def test_camera_oracle_is_the_oracle_plus_one_function():
-    text = camera_ref.SRC.read_text()
+    text = ref_lib.SRC.read_text()
     assert text.count("#include") == 1 and '#include "../../oracle/raingun_oracle.c"' in text
-    cc, flags = camera_ref.oracle_flags()
-    assert all(f in flags for f in camera_ref.REQUIRED_FLAGS)
+    cc, flags = ref_lib.oracle_flags()
+    assert all(f in flags for f in ref_lib.REQUIRED_FLAGS)
     # nothing of the product includes or loads it
     for p in (REPO / "raingun_amd").rglob("*"):
         if p.is_file() and p.suffix in (".py", ".h", ".hip", ".cpp", ".c") or p.name == "Makefile":
-            assert "camera_oracle" not in p.read_text(errors="replace"), p
+            text = p.read_text(errors="replace")
+            assert "ref_frames" not in text and "ref_lib" not in text and "camera_oracle" not in text, p
 
 
 # ---------------------------------------------------------------- 3. flags and look_at

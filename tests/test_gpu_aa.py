@@ -11,7 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from raingun_amd import _abi, _host, aa
+from gpu_launch import assert_same_pixels, native_cli_path, png, require_device
+from raingun_amd import _abi, aa
 from raingun_amd.color import Color
 from raingun_amd.scene import AABB, DeviceScene, Material, Scene, SceneDesc
 from raingun_amd.synth import synthetic_scene
@@ -23,8 +24,7 @@ RGB_TOL = 1e-4  # the project's per-channel bound on pre-quantisation f32 RGB
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 # ---------------------------------------------------------------- 1. the resolve kernel alone
@@ -120,8 +120,7 @@ def test_supersampled_frame_matches_oracle(oracle_lib, example_scenes, name, pat
             ds.set_aa_band_rows(band_rows)
             st = _abi.rg_stats()
             rgba, mean = ds.render_image_aa(w, h, k, want_rgb=True, stats=st)
-            mism = np.count_nonzero((rgba != want_rgba).any(axis=2))
-            assert mism == 0, f"band rows {band_rows}: {mism} RGBA8 pixels differ"
+            assert_same_pixels(rgba, want_rgba, f"band rows {band_rows}")
             diff = float(np.abs(mean.astype(np.float64) - want_mean.astype(np.float64)).max())
             assert diff <= RGB_TOL, f"band rows {band_rows}: f32 means differ by {diff}"
             assert st.rays.as_dict() == want_counts, f"band rows {band_rows}: ray counts differ"
@@ -240,17 +239,9 @@ def test_argument_errors(example_scenes):
 
 
 # ---------------------------------------------------------------- 7. command lines
-def _png(path):
-    from PIL import Image
-
-    return np.asarray(Image.open(path).convert("RGBA"))
-
-
 @pytest.fixture(scope="module")
 def native_cli():
-    if not _host.CLI_PATH.exists():
-        subprocess.run(["make", "-s", "-C", str(_host.SRC_DIR)], check=True)
-    return str(_host.CLI_PATH)
+    return native_cli_path()
 
 
 def test_native_cli_samples(native_cli, oracle_lib, example_scenes, golden_dir, tmp_path):
@@ -260,7 +251,7 @@ def test_native_cli_samples(native_cli, oracle_lib, example_scenes, golden_dir, 
     r = subprocess.run([native_cli, "--samples", "2", "-w", "160", "-h", "90", yml, "-o", str(out)],
                        cwd=golden_dir, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
-    assert np.array_equal(_png(out), want_rgba)
+    assert np.array_equal(png(out), want_rgba)
     r = subprocess.run([native_cli, "--samples", "x", yml, "-o", str(out)], cwd=golden_dir, capture_output=True,
                        text=True, timeout=60)
     assert r.returncode == 101 and "Could not parse samples" in r.stderr
@@ -280,4 +271,4 @@ def test_python_cli_samples(oracle_lib, example_scenes, golden_dir, tmp_path, mo
     monkeypatch.chdir(golden_dir)  # textures resolve against the working directory
     assert main(["--samples", "2", "-w", "160", "-h", "90", str(golden_dir / "examples" / "test1.yml"),
                  "-o", str(out)]) == 0
-    assert np.array_equal(_png(out), want_rgba)
+    assert np.array_equal(png(out), want_rgba)

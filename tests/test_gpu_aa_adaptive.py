@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_launch import assert_same_pixels, require_device
 from raingun_amd import _abi, aa
 from raingun_amd.color import Color
 from raingun_amd.scene import AABB, DeviceScene, Material, Scene, SceneDesc
@@ -21,8 +22,7 @@ RGB_TOL = 1e-4  # the project's per-channel bound on pre-quantisation f32 RGB
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 # ---------------------------------------------------------------- 1. the mask kernel alone
@@ -124,8 +124,7 @@ def test_adaptive_frame_matches_oracle(oracle_lib, example_scenes, name, path, w
             st = _abi.rg_stats()
             rgba, mean, mask = ds.render_image_aa_adaptive(w, h, k, t, want_rgb=True, want_mask=True, stats=st)
             assert np.array_equal(mask, want_mask), f"band rows {band_rows}: {np.count_nonzero(mask != want_mask)} mask bytes differ"
-            mism = np.count_nonzero((rgba != want_rgba).any(axis=2))
-            assert mism == 0, f"band rows {band_rows}: {mism} RGBA8 pixels differ"
+            assert_same_pixels(rgba, want_rgba, f"band rows {band_rows}")
             diff = float(np.abs(mean.astype(np.float64) - want_mean.astype(np.float64)).max())
             assert diff <= RGB_TOL, f"band rows {band_rows}: f32 means differ by {diff}"
             rays = st.rays.as_dict()

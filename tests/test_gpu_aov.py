@@ -13,10 +13,10 @@ import subprocess
 
 import numpy as np
 import pytest
-from PIL import Image
 
 import aov_ref
-from raingun_amd import _abi, _host, aov
+from gpu_launch import native_cli_path, png, require_device
+from raingun_amd import _abi, aov
 from raingun_amd.camera import Camera
 from raingun_amd.color import Color
 from raingun_amd.scene import AABB, DeviceScene, Material, Scene, Sphere
@@ -32,8 +32,7 @@ TILINGS = ((8, 3, 1), (16, 2, 0))
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 def _ref(example_scenes, name, w, h, cam=None, **tiling):
@@ -346,7 +345,7 @@ def _check_cli_outputs(example_scenes, tmp_path, stem, plain):
     cam = Camera.look_at((3, 2, -10), (0, 0, -30))
     ref = _ref(example_scenes, "test1", w, h, cam)[1]
     for n in aov.LAYERS:
-        got = np.asarray(Image.open(tmp_path / f"{stem}.{n}.png").convert("RGBA"))
+        got = png(tmp_path / f"{stem}.{n}.png")
         want = aov.visualize(n, ref[n])
         assert np.array_equal(got, want), (n, int((got != want).any(axis=2).sum()))
     assert (tmp_path / f"{stem}.png").read_bytes() == plain.read_bytes()
@@ -356,9 +355,7 @@ CLI_FLAGS = ["--draft", "--eye", "3,2,-10", "--look-at=0,0,-30"]
 
 
 def test_native_cli_aov(example_scenes, golden_dir, tmp_path):
-    if not _host.CLI_PATH.exists():
-        subprocess.run(["make", "-s", "-C", str(_host.SRC_DIR)], check=True)
-    cli, yml = str(_host.CLI_PATH), str(golden_dir / "examples" / "test1.yml")
+    cli, yml = native_cli_path(), str(golden_dir / "examples" / "test1.yml")
     plain = tmp_path / "plain.png"
     for flags, out in (([], plain), (["--aov", "all"], tmp_path / "cli.png")):
         r = subprocess.run([cli, *CLI_FLAGS, *flags, "-o", str(out), yml], cwd=golden_dir, capture_output=True, text=True,
@@ -386,4 +383,4 @@ def test_python_cli_aov(example_scenes, golden_dir, tmp_path, monkeypatch):
     assert sorted(p.name for p in tmp_path.glob("two*.png")) == ["two.body.png", "two.depth.png", "two.png"]
     ref = _ref(example_scenes, "test1", 97, 61)[1]
     for n in ("body", "depth"):  # one ray per pixel whatever --samples says
-        assert np.array_equal(np.asarray(Image.open(tmp_path / f"two.{n}.png").convert("RGBA")), aov.visualize(n, ref[n]))
+        assert np.array_equal(png(tmp_path / f"two.{n}.png"), aov.visualize(n, ref[n]))

@@ -12,10 +12,10 @@ import subprocess
 
 import numpy as np
 import pytest
-from PIL import Image
 
 import camera_ref
-from raingun_amd import _abi, _host, aa
+from gpu_launch import assert_same_pixels, device_launch, native_cli_path, png, require_device
+from raingun_amd import _abi, aa
 from raingun_amd.camera import Camera
 from raingun_amd.color import Color
 from raingun_amd.scene import (AABB, DeviceScene, DirectionalLight, Material, Plane, Scene, SceneDesc, Sphere,
@@ -31,8 +31,7 @@ WHITE = Color.from_str("#ffffff")
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 # ---------------------------------------------------------------- scenes and poses
@@ -105,8 +104,7 @@ def _ref(example_scenes, name, cam, w, h, **tiling):
 
 def _assert_frame(got_rgba, got_rgb, got_counts, ref, what):
     st, rgba, rgb, counts, err = ref
-    mism = int(np.count_nonzero((got_rgba != rgba).any(axis=2)))
-    assert mism == 0, f"{what}: {mism} RGBA8 pixels differ"
+    assert_same_pixels(got_rgba, rgba, what)
     if got_rgb is not None:
         diff = float(np.abs(got_rgb.astype(np.float64) - rgb.astype(np.float64)).max())
         assert diff <= RGB_TOL, f"{what}: f32 RGB differs by {diff}"
@@ -130,20 +128,6 @@ def _compare(example_scenes, name, cam, w, h, bvh=None):
 
 
 # ---------------------------------------------------------------- 4. the identity camera, set explicitly
-def _device_launch(ds, w, h):
-    """One device-resident launch of the whole frame -> (rgba, ray counts, ran PLAIN)."""
-    import torch
-
-    t = _abi.rg_tiling(h, 1, 0)
-    rgba = torch.full((h, w, 4), 7, dtype=torch.uint8, device="cuda")
-    st = _abi.rg_stats()
-    _abi.check(_abi.lib().rg_render_tiles_async(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), None, None,
-                                                C.byref(st)))
-    plain = ds.last_plain()
-    torch.cuda.synchronize()
-    return rgba.cpu().numpy(), st.rays.as_dict(), plain
-
-
 @pytest.mark.parametrize("name,w,h", [("test1", 200, 150), ("test2", 200, 150), ("test3", 200, 150), ("synth64", 97, 61)])
 def test_identity_camera_is_no_camera(oracle_lib, example_scenes, name, w, h):
     scene = _scene(example_scenes, name)
@@ -153,7 +137,7 @@ def test_identity_camera_is_no_camera(oracle_lib, example_scenes, name, w, h):
         ds = DeviceScene(scene, path=path)
         try:
             st0, st1 = _abi.rg_stats(), _abi.rg_stats()
-            plain_initial = _device_launch(ds, w, h)[2]
+            plain_initial = device_launch(ds, w, h).plain
             rgba0, rgb0 = ds.render_tiles(w, h, want_rgb=True, stats=st0)
             ds.set_camera(Camera.identity())
             rgba1, rgb1 = ds.render_tiles(w, h, want_rgb=True, stats=st1)
@@ -162,19 +146,19 @@ def test_identity_camera_is_no_camera(oracle_lib, example_scenes, name, w, h):
             assert st1.rays.as_dict() == st0.rays.as_dict() == o_counts, (name, path)
             # device-resident launches: PLAIN without a camera (light scenes that qualify), never with
             # one, and again after the reset -- the scene launches what it launched before
-            base, counts, plain_before = _device_launch(ds, w, h)
+            base, counts, plain_before, _ = device_launch(ds, w, h)
             assert plain_before is False
             ds.set_camera(None)
-            again, counts_again, plain_after = _device_launch(ds, w, h)
+            again, counts_again, plain_after, _ = device_launch(ds, w, h)
             assert np.array_equal(base, o_rgba) and np.array_equal(again, o_rgba)
             assert counts == counts_again == o_counts
             assert plain_after == plain_initial, "set_camera(None) did not bring the scene's own kernel back"
             if name == "test1" and path == _abi.PATH_LIGHT:
                 # a frame size whose PLAIN launch tests/test_gpu_light_plain.py pins
                 ds.set_camera(Camera.identity())
-                assert _device_launch(ds, 97, 61)[2] is False
+                assert device_launch(ds, 97, 61).plain is False
                 ds.set_camera(None)
-                assert _device_launch(ds, 97, 61)[2] is True, "set_camera(None) did not bring the PLAIN kernel back"
+                assert device_launch(ds, 97, 61).plain is True, "set_camera(None) did not bring the PLAIN kernel back"
         finally:
             ds.close()
 
@@ -439,9 +423,7 @@ def test_abi_rejections(example_scenes):
 
 # ---------------------------------------------------------------- 10. the raingun binary, and cli.py
 def test_native_cli_camera_flags(example_scenes, golden_dir, tmp_path):
-    if not _host.CLI_PATH.exists():
-        subprocess.run(["make", "-s", "-C", str(_host.SRC_DIR)], check=True)
-    cli, yml = str(_host.CLI_PATH), str(golden_dir / "examples" / "test2.yml")
+    cli, yml = native_cli_path(), str(golden_dir / "examples" / "test2.yml")
     w, h = 97, 61
     cam = Camera.look_at((3, 2, -10), (0, 0, -30))
     ref = _ref(example_scenes, "test2", cam, w, h)
@@ -449,12 +431,12 @@ def test_native_cli_camera_flags(example_scenes, golden_dir, tmp_path):
     r = subprocess.run([cli, "-w", str(w), "-h", str(h), "--eye", "3,2,-10", "--look-at=0,0,-30", "-o", str(out), yml],
                        cwd=golden_dir, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
-    assert np.array_equal(np.asarray(Image.open(out).convert("RGBA")), ref[1])
+    assert np.array_equal(png(out), ref[1])
     ref = _ref(example_scenes, "test2", Camera.at((-1.0, 2.0, 3.0)), w, h)
     r = subprocess.run([cli, "-w", str(w), "-h", str(h), "--eye", "-1,2,3", "-o", str(out), yml],
                        cwd=golden_dir, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
-    assert np.array_equal(np.asarray(Image.open(out).convert("RGBA")), ref[1])
+    assert np.array_equal(png(out), ref[1])
     bad_width = subprocess.run([cli, "--samples", "9", yml], capture_output=True, text=True, timeout=60)
     for flags in (["--eye", "1,2"], ["--eye", "1,2,x"], ["--look-at", "1,2,3", "--eye", "1,2,3"], ["--up", "0,1,0"],
                   ["--look-at", "0,0,-5", "--up", "0,0,1"], ["--eye"]):
@@ -472,6 +454,6 @@ def test_python_cli_camera_flags(example_scenes, golden_dir, tmp_path):
     out = tmp_path / "cam.png"
     assert main([str(golden_dir / "examples" / "test2.yml"), "-w", str(w), "-h", str(h), "--eye", "3,2,-10",
                  "--look-at", "0,0,-30", "--up", "0.1,1,0", "-o", str(out)]) == 0
-    assert np.array_equal(np.asarray(Image.open(out).convert("RGBA")), ref[1])
+    assert np.array_equal(png(out), ref[1])
     scene = _scene(example_scenes, "test2")
     assert np.array_equal(scene.render_image(w, h, camera=cam), ref[1])

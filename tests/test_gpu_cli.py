@@ -9,21 +9,15 @@ import numpy as np
 import pytest
 from PIL import Image
 
-from raingun_amd import _abi, _host
+from gpu_launch import native_cli_path, png
 from raingun_amd.cli import main
 
 pytestmark = pytest.mark.gpu
 
 
-def _png(path):
-    return np.asarray(Image.open(path).convert("RGBA"))
-
-
 @pytest.fixture(scope="module")
 def native_cli():
-    if not _host.CLI_PATH.exists():
-        subprocess.run(["make", "-s", "-C", str(_host.SRC_DIR)], check=True)
-    return str(_host.CLI_PATH)
+    return native_cli_path()
 
 
 @pytest.mark.parametrize("name", ["test1", "test2", "test3"])
@@ -34,7 +28,7 @@ def test_native_cli_reproduces_golden(native_cli, golden_dir, tmp_path, name):
                        cwd=golden_dir, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     assert "\t→\t" in r.stdout and "render" in r.stdout and "write" in r.stdout
-    assert np.array_equal(_png(out), _png(golden_dir / "examples" / f"{name}.png"))
+    assert np.array_equal(png(out), png(golden_dir / "examples" / f"{name}.png"))
 
 
 def test_native_cli_default_output_name_and_draft(native_cli, golden_dir, tmp_path):
@@ -51,7 +45,7 @@ def test_native_cli_default_output_name_and_draft(native_cli, golden_dir, tmp_pa
 def test_python_cli_renders_golden_test2(golden_dir, tmp_path, capsys):
     out = tmp_path / "test2.png"
     assert main([str(golden_dir / "examples" / "test2.yml"), "-o", str(out)]) == 0
-    assert np.array_equal(_png(out), _png(golden_dir / "examples" / "test2.png"))
+    assert np.array_equal(png(out), png(golden_dir / "examples" / "test2.png"))
     line = capsys.readouterr().out
     assert "→" in line and "render" in line and "write" in line
 

@@ -15,6 +15,7 @@ import time
 import numpy as np
 import pytest
 
+from gpu_launch import require_device
 from raingun_amd import _abi
 from raingun_amd.color import Color
 from raingun_amd.scene import (AABB, DeviceScene, DirectionalLight, Material, Plane, Scene, SceneDesc, Sphere,
@@ -29,7 +30,7 @@ WHITE = Color.from_str("#ffffff")
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    assert _abi.lib().rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 def _oracle(oracle_lib, scene, w, h):

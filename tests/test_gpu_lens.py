@@ -13,10 +13,10 @@ import subprocess
 
 import numpy as np
 import pytest
-from PIL import Image
 
 import lens_ref
-from raingun_amd import _abi, _host
+from gpu_launch import assert_same_pixels, native_cli_path, png, require_device
+from raingun_amd import _abi
 from raingun_amd.camera import Camera, Lens
 from raingun_amd.color import Color
 from raingun_amd.scene import AABB, DeviceScene, Material, Scene
@@ -34,8 +34,7 @@ INVALID = _abi.RG_ERR_INVALID_ARGUMENT
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 _SCENES = {}
@@ -59,8 +58,7 @@ def _ref(example_scenes, name, cam, lens, w, h, k):
 
 def _assert_frame(got_rgba, got_mean, got_counts, ref, what):
     st, rgba, mean, counts, err = ref
-    mism = int(np.count_nonzero((got_rgba != rgba).any(axis=2)))
-    assert mism == 0, f"{what}: {mism} RGBA8 pixels differ"
+    assert_same_pixels(got_rgba, rgba, what)
     if got_mean is not None:
         diff = float(np.abs(got_mean.astype(np.float64) - mean.astype(np.float64)).max())
         assert diff <= RGB_TOL, f"{what}: f32 means differ by {diff}"
@@ -256,22 +254,20 @@ def test_aabb_normal_error_through_a_lens(path):
 
 # ---------------------------------------------------------------- 5. the raingun binary, and cli.py
 def test_native_cli_lens_flags(example_scenes, golden_dir, tmp_path):
-    if not _host.CLI_PATH.exists():
-        subprocess.run(["make", "-s", "-C", str(_host.SRC_DIR)], check=True)
-    cli, yml = str(_host.CLI_PATH), str(golden_dir / "examples" / "test2.yml")
+    cli, yml = native_cli_path(), str(golden_dir / "examples" / "test2.yml")
     w, h, k = 40, 30, 2
     out = tmp_path / "lens.png"
     ref = _ref(example_scenes, "test2", None, Lens(0.5, 30.0), w, h, k)
     r = subprocess.run([cli, "-w", str(w), "-h", str(h), "--samples", str(k), "--aperture", "0.5", "--focus=30", "-o", str(out), yml],
                        cwd=golden_dir, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
-    assert np.array_equal(np.asarray(Image.open(out).convert("RGBA")), ref[1])
+    assert np.array_equal(png(out), ref[1])
     ref = _ref(example_scenes, "test2", LOOK, Lens(0.25, 20.0), w, h, k)
     r = subprocess.run([cli, "-w", str(w), "-h", str(h), "--samples", str(k), "--eye", "3,2,-10", "--look-at", "0,0,-30",
                         "--aperture", "0.25", "--focus", "20", "-o", str(out), yml],
                        cwd=golden_dir, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
-    assert np.array_equal(np.asarray(Image.open(out).convert("RGBA")), ref[1])
+    assert np.array_equal(png(out), ref[1])
     bad_width = subprocess.run([cli, "--samples", "9", yml], capture_output=True, text=True, timeout=60)
     for flags in (["--aperture", "0.5"], ["--samples", "2", "--focus", "3"], ["--aperture", "0.5", "--focus", "3"],
                   ["--samples", "1", "--aperture", "0.5", "--focus", "3"],
@@ -292,7 +288,7 @@ def test_python_cli_lens_flags(example_scenes, golden_dir, tmp_path):
     out = tmp_path / "lens.png"
     assert main([str(golden_dir / "examples" / "test2.yml"), "-w", str(w), "-h", str(h), "--samples", str(k), "--eye", "3,2,-10",
                  "--look-at", "0,0,-30", "--aperture", "0.25", "--focus", "20", "-o", str(out)]) == 0
-    assert np.array_equal(np.asarray(Image.open(out).convert("RGBA")), ref[1])
+    assert np.array_equal(png(out), ref[1])
     scene = copy.copy(_scene(example_scenes, "test2"))
     scene.set_lens(Lens(0.25, 20.0))  # Scene.set_lens: every DeviceScene of the scene starts with it
     assert np.array_equal(scene.render_image(w, h, samples=k, camera=LOOK), ref[1])

@@ -8,25 +8,22 @@ buffers): RGBA8 byte for byte, per-class ray counts equal, and the debug query
 tiles-per-wave grid (TPW 0).  Scenes that miss exactly one PLAIN condition must take the old kernel.
 """
 import copy
-import ctypes as C
 
 import numpy as np
 import pytest
 
-from raingun_amd import _abi
+from gpu_launch import SIZES, assert_same_pixels, device_launch, oracle_frame, require_device
 from raingun_amd.color import Color
-from raingun_amd.scene import DeviceScene, DirectionalLight, Disk, Material, Scene, SceneDesc, Sphere, SphericalLight
+from raingun_amd.scene import DeviceScene, DirectionalLight, Disk, Material, Scene, Sphere, SphericalLight
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [(97, 61), (64, 40)]  # partial 8x8 tiles at the right and bottom edges; whole tiles
 DEPTHS = [0, 1, 5]
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 def _test1(example_scenes, lights=3, depth=5):
@@ -47,58 +44,16 @@ def _pair_scene():
                  default_color=Color.from_str("#203040"), max_recursion_depth=5)
 
 
-_ORACLE = {}
-
-
-def _oracle(oracle_lib, key, scene, w, h):
-    """The CPU restatement's frame and ray counts, computed once per (scene, size) and shared."""
-    k = (key, w, h)
-    if k not in _ORACLE:
-        o_st, o_rgba, _, o_counts, _ = oracle_lib.render(SceneDesc(scene), w, h)
-        assert o_st == 0
-        o_rgba.setflags(write=False)
-        _ORACLE[k] = (o_rgba, o_counts)
-    return _ORACLE[k]
-
-
-def _render(ds, w, h, mode="single", want_rgb=False, stream=None):
-    """One device-resident launch of the whole frame -> (rgba, ray counts, ran PLAIN)."""
-    import torch
-
-    lib = _abi.lib()
-    t = _abi.rg_tiling(h, 1, 0)
-    rgba = torch.full((h, w, 4), 7, dtype=torch.uint8, device="cuda")
-    rgb = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda") if want_rgb else None
-    sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
-    rp = C.c_void_p(rgb.data_ptr()) if want_rgb else None
-    if mode == "single":
-        st = _abi.rg_stats()
-        _abi.check(lib.rg_render_tiles_async(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), rp, sp,
-                                             C.byref(st)))
-        counts = st.rays.as_dict()
-    else:
-        _abi.check(lib.rg_render_tiles_pipelined(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), rp, sp))
-        torch.cuda.synchronize()
-        words = (C.c_uint64 * 16)()
-        _abi.check(lib.rg_debug_counters(ds.handle, words))
-        assert words[3] == 0, "the launch reported an error"
-        counts = {"primary": words[0], "shadow": words[1], "secondary": words[2]}
-    plain = ds.last_plain()
-    torch.cuda.synchronize()
-    return rgba.cpu().numpy(), counts, plain
-
-
 def _check(oracle_lib, key, scene, w, h, mode, expect_plain, want_rgb=False, prepare=None):
-    o_rgba, o_counts = _oracle(oracle_lib, key, scene, w, h)
+    o_rgba, o_counts = oracle_frame(oracle_lib, key, scene, w, h)
     ds = DeviceScene(scene)
     if prepare:
         prepare(ds)
-    rgba, counts, plain = _render(ds, w, h, mode, want_rgb)
+    rgba, counts, plain, _ = device_launch(ds, w, h, mode, want_rgb=want_rgb)
     ds.close()
     assert plain == expect_plain, f"ran the {'PLAIN' if plain else 'general'} kernel"
     assert counts == o_counts, "ray counts differ"
-    mism = np.count_nonzero((rgba != o_rgba).any(axis=2))
-    assert mism == 0, f"{mism} RGBA8 pixels differ"
+    assert_same_pixels(rgba, o_rgba)
 
 
 @pytest.mark.parametrize("mode", ["single", "pipelined"])
@@ -170,12 +125,12 @@ def test_switching_kernels_on_one_stream_and_handle(oracle_lib, example_scenes):
 
     w, h = 97, 61
     scene = _test1(example_scenes, 3, 5)
-    o_rgba, o_counts = _oracle(oracle_lib, ("test1", 3, 5), scene, w, h)
+    o_rgba, o_counts = oracle_frame(oracle_lib, ("test1", 3, 5), scene, w, h)
     ds = DeviceScene(scene)
     stream = torch.cuda.Stream()
     first = {}
     for want_rgb in (False, True, False, True, False):
-        rgba, counts, plain = _render(ds, w, h, "single", want_rgb, stream)
+        rgba, counts, plain, _ = device_launch(ds, w, h, "single", want_rgb=want_rgb, stream=stream)
         assert plain == (not want_rgb)
         assert counts == o_counts
         assert np.array_equal(rgba, first.setdefault(want_rgb, rgba))

@@ -10,6 +10,7 @@ import copy
 import numpy as np
 import pytest
 
+from gpu_launch import assert_same_pixels, png, require_device
 from raingun_amd import _abi
 from raingun_amd.scene import AABB, DeviceScene, Material, Scene, SceneDesc
 from raingun_amd.color import Color
@@ -22,8 +23,7 @@ RGB_TOL = 1e-4  # per-channel |delta| bound stated by the north_star
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 def _compare(oracle_lib, scene, w, h, tile_rows=0, stride=1, offset=0, path=None, bvh=None, lane=None,
@@ -41,8 +41,7 @@ def _compare(oracle_lib, scene, w, h, tile_rows=0, stride=1, offset=0, path=None
     assert st.rays.as_dict() == o_counts, "ray counts differ"
     diff = np.abs(g_rgb.astype(np.float64) - o_rgb.astype(np.float64))
     assert np.nanmax(diff) <= RGB_TOL
-    mism = np.count_nonzero((g_rgba != o_rgba).any(axis=2))
-    assert mism == 0, f"{mism} RGBA8 pixels differ"
+    assert_same_pixels(g_rgba, o_rgba)
     ds.close()
     return st
 
@@ -68,13 +67,10 @@ def test_examples_800x600(oracle_lib, example_scenes, name, path):
 def test_examples_reproduce_reference_golden_png(example_scenes, golden_dir, name, path):
     """The GPU output equals the reference's own renders byte for byte
     (examples/test{1,2,3}.png, 800x600, YAML depth), textures included."""
-    from PIL import Image
-
     ds = DeviceScene(example_scenes[name], path=path)
     got = ds.render_image(800, 600)
     ds.close()
-    gold = np.asarray(Image.open(golden_dir / "examples" / f"{name}.png").convert("RGBA"))
-    assert np.array_equal(got, gold)
+    assert np.array_equal(got, png(golden_dir / "examples" / f"{name}.png"))
 
 
 def test_config2_test1_4k_depth5(oracle_lib, example_scenes):

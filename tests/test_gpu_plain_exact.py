@@ -13,32 +13,29 @@ tile start from the magic of tiles per row.  Everything must stay bit for bit:
   * with the quotient check switched off the launch takes the general kernel and stays exact.
 """
 import copy
-import ctypes as C
 
 import numpy as np
 import pytest
 
+import gpu_launch
+from gpu_launch import SIZES, assert_same_pixels, device_launch, oracle_frame, require_device
 from raingun_amd import _abi
 from raingun_amd.color import Color
-from raingun_amd.scene import (DeviceScene, DirectionalLight, Material, Plane, Scene, SceneDesc, Sphere,
+from raingun_amd.scene import (DeviceScene, DirectionalLight, Material, Plane, Scene, Sphere,
                                SphericalLight, Texture)
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [(97, 61), (64, 40)]  # partial 8x8 tiles at the right and bottom edges; whole tiles
-
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 # ---------------------------------------------------------------- the camera ray, both ways
 @pytest.fixture(scope="module")
 def any_scene():
-    ds = DeviceScene(Scene(bodies=[Sphere((0.0, 0.0, -5.0), 1.0, Material(Color.from_str("#ffffff"), 0.5))],
-                           lights=[DirectionalLight((0.0, -1.0, -1.0), Color.from_str("#ffffff"), 1.0)]))
+    ds = DeviceScene(gpu_launch.any_scene())
     yield ds
     ds.close()
 
@@ -98,56 +95,16 @@ def _scenes(example_scenes):
     }
 
 
-_ORACLE = {}
-
-
-def _oracle(oracle_lib, key, scene, w, h):
-    """The CPU restatement's whole frame and ray counts, computed once per (scene, size) and shared."""
-    k = (key, w, h)
-    if k not in _ORACLE:
-        o_st, o_rgba, _, o_counts, _ = oracle_lib.render(SceneDesc(scene), w, h)
-        assert o_st == 0
-        o_rgba.setflags(write=False)
-        _ORACLE[k] = (o_rgba, o_counts)
-    return _ORACLE[k]
-
-
-def _render(ds, w, h, mode, tiling=None):
-    """One device-resident launch -> (rows, ray counts, ran PLAIN)."""
-    import torch
-
-    lib = _abi.lib()
-    t = tiling if tiling is not None else _abi.rg_tiling(h, 1, 0)
-    rows = lib.rg_tiling_rows(h, C.byref(t))
-    rgba = torch.full((rows, w, 4), 7, dtype=torch.uint8, device="cuda")
-    if mode == "single":
-        st = _abi.rg_stats()
-        _abi.check(lib.rg_render_tiles_async(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), None, None,
-                                             C.byref(st)))
-        counts = st.rays.as_dict()
-    else:
-        _abi.check(lib.rg_render_tiles_pipelined(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), None, None))
-        torch.cuda.synchronize()
-        words = (C.c_uint64 * 16)()
-        _abi.check(lib.rg_debug_counters(ds.handle, words))
-        assert words[3] == 0, "the launch reported an error"
-        counts = {"primary": words[0], "shadow": words[1], "secondary": words[2]}
-    plain = ds.last_plain()
-    torch.cuda.synchronize()
-    return rgba.cpu().numpy(), counts, plain
-
-
 def _check_frame(oracle_lib, key, scene, w, h, mode, expect_plain=True, prepare=None):
-    o_rgba, o_counts = _oracle(oracle_lib, key, scene, w, h)
+    o_rgba, o_counts = oracle_frame(oracle_lib, key, scene, w, h)
     ds = DeviceScene(scene)
     if prepare:
         prepare(ds)
-    rgba, counts, plain = _render(ds, w, h, mode)
+    rgba, counts, plain, _ = device_launch(ds, w, h, mode)
     ds.close()
     assert plain == expect_plain, f"ran the {'PLAIN' if plain else 'general'} kernel"
     assert counts == o_counts, "ray counts differ"
-    mism = np.count_nonzero((rgba != o_rgba).any(axis=2))
-    assert mism == 0, f"{mism} RGBA8 pixels differ"
+    assert_same_pixels(rgba, o_rgba)
 
 
 @pytest.mark.parametrize("mode", ["single", "pipelined"])
@@ -175,10 +132,10 @@ def test_shares_equal_the_frames_rows(oracle_lib, example_scenes, tile_rows, str
     last tile alone; 3 rows per tile are no power of two."""
     w, h = 97, 61
     scene = _scenes(example_scenes)["spheres"]
-    o_rgba, _ = _oracle(oracle_lib, "spheres", scene, w, h)
+    o_rgba, _ = oracle_frame(oracle_lib, "spheres", scene, w, h)
     t = _abi.rg_tiling(tile_rows, stride, offset)
     ds = DeviceScene(scene)
-    rgba, _, plain = _render(ds, w, h, mode, t)
+    rgba, _, plain, _ = device_launch(ds, w, h, mode, t)
     ds.close()
     assert plain, "a share must stay on the PLAIN kernel"
     tiles = list(range(offset, (h + tile_rows - 1) // tile_rows, stride))
@@ -187,8 +144,7 @@ def test_shares_equal_the_frames_rows(oracle_lib, example_scenes, tile_rows, str
     for k, ti in enumerate(tiles):
         n = min(tile_rows, h - ti * tile_rows)
         want[k * tile_rows:k * tile_rows + n] = o_rgba[ti * tile_rows:ti * tile_rows + n]
-    mism = np.count_nonzero((rgba != want).any(axis=2))
-    assert mism == 0, f"{mism} RGBA8 pixels differ"
+    assert_same_pixels(rgba, want)
 
 
 # ---------------------------------------------------------------- the check refused
@@ -200,12 +156,12 @@ def test_quotient_check_failed_takes_the_general_kernel(oracle_lib, example_scen
     again, the same handle is back on the PLAIN kernel."""
     scene = _scenes(example_scenes)["oblique"]
     _check_frame(oracle_lib, "oblique", scene, w, h, mode, expect_plain=False, prepare=lambda ds: ds.set_exact_div(False))
-    o_rgba, o_counts = _oracle(oracle_lib, "oblique", scene, w, h)
+    o_rgba, o_counts = oracle_frame(oracle_lib, "oblique", scene, w, h)
     ds = DeviceScene(scene)
     seen = []
     for enable in (False, True, False):
         ds.set_exact_div(enable)
-        rgba, counts, plain = _render(ds, w, h, mode)
+        rgba, counts, plain, _ = device_launch(ds, w, h, mode)
         seen.append(plain)
         assert counts == o_counts and np.array_equal(rgba, o_rgba)
     ds.close()

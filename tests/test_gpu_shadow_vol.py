@@ -7,26 +7,24 @@ byte for byte with the CPU restatement and with each other, with equal ray count
 name the kernel (rg_debug_last_plain) and say whether it ran with the volume
 (rg_debug_last_shadow_volume), so no case passes on another path."""
 import copy
-import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+from gpu_launch import SIZES, assert_same_pixels, device_launch, oracle_frame, require_device
 from raingun_amd import _abi
 from raingun_amd.color import Color
-from raingun_amd.scene import DeviceScene, DirectionalLight, Material, Plane, Scene, SceneDesc, Sphere, SphericalLight
+from raingun_amd.scene import DeviceScene, DirectionalLight, Material, Plane, Scene, Sphere, SphericalLight
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [(97, 61), (64, 40)]  # partial 8x8 tiles at the right and bottom edges; whole tiles
 MODES = ["single", "pipelined"]
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 def _test1(example_scenes, lights=3, depth=5, fov=None):
@@ -94,63 +92,23 @@ def _seventeen_spheres():
                  default_color=_col("#203040"), max_recursion_depth=3)
 
 
-_ORACLE = {}
-
-
-def _oracle(oracle_lib, key, scene, w, h):
-    """The CPU restatement's frame and ray counts, computed once per (scene, size) and shared."""
-    k = (key, w, h)
-    if k not in _ORACLE:
-        o_st, o_rgba, _, o_counts, _ = oracle_lib.render(SceneDesc(scene), w, h)
-        assert o_st == 0
-        o_rgba.setflags(write=False)
-        _ORACLE[k] = (o_rgba, o_counts)
-    return _ORACLE[k]
-
-
-def _render(ds, w, h, mode, tiling=None):
-    """One device-resident launch -> (rgba rows, ray counts, ran PLAIN, ran with the volume)."""
-    import torch
-
-    lib = _abi.lib()
-    t = tiling or _abi.rg_tiling(h, 1, 0)
-    rows = lib.rg_tiling_rows(h, C.byref(t))
-    rgba = torch.full((rows, w, 4), 7, dtype=torch.uint8, device="cuda")
-    if mode == "single":
-        st = _abi.rg_stats()
-        _abi.check(lib.rg_render_tiles_async(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), None, None,
-                                             C.byref(st)))
-        counts = st.rays.as_dict()
-    else:
-        _abi.check(lib.rg_render_tiles_pipelined(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), None, None))
-        torch.cuda.synchronize()
-        words = (C.c_uint64 * 16)()
-        _abi.check(lib.rg_debug_counters(ds.handle, words))
-        assert words[3] == 0, "the launch reported an error"
-        counts = {"primary": words[0], "shadow": words[1], "secondary": words[2]}
-    plain, used = ds.last_plain(), ds.last_shadow_volume()
-    torch.cuda.synchronize()
-    return rgba.cpu().numpy(), counts, plain, used
-
-
 def _check(oracle_lib, key, scene, w, h, mode, volume=True, plain=True):
-    o_rgba, o_counts = _oracle(oracle_lib, key, scene, w, h)
+    o_rgba, o_counts = oracle_frame(oracle_lib, key, scene, w, h)
     ds = DeviceScene(scene)
     info = ds.shadow_volume_info()
     assert info["built"] == volume and info["enabled"] == volume
     if volume:
         assert info["g"] ** 3 * 4 == info["bytes"] and 0.0 < info["set_share"] < 1.0
-    on = _render(ds, w, h, mode)
+    on = device_launch(ds, w, h, mode)
     ds.set_shadow_volume(False)
-    off = _render(ds, w, h, mode)
+    off = device_launch(ds, w, h, mode)
     ds.close()
     if plain is not None:
         assert (on[2], off[2]) == (plain, plain), f"ran the {'PLAIN' if on[2] else 'general'} kernel"
     assert (on[3], off[3]) == (volume, False), "which launch ran with the volume"
     assert on[1] == o_counts and off[1] == o_counts, "ray counts differ"
     assert np.array_equal(on[0], off[0]), "the frame differs from the same launch without the volume"
-    mism = np.count_nonzero((on[0] != o_rgba).any(axis=2))
-    assert mism == 0, f"{mism} RGBA8 pixels differ from the CPU restatement"
+    assert_same_pixels(on[0], o_rgba, "against the CPU restatement")
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -167,11 +125,11 @@ def test_eighth_share_against_the_whole_frame(oracle_lib, example_scenes, share,
     """Rows r, r + 8, ... of 8-row tiles (a 1/8 share of rg_render_multi) against the whole frame's rows."""
     w, h = 97, 61
     scene = _test1(example_scenes)
-    o_rgba, _ = _oracle(oracle_lib, ("test1", 3, 5), scene, w, h)
+    o_rgba, _ = oracle_frame(oracle_lib, ("test1", 3, 5), scene, w, h)
     ds = DeviceScene(scene)
-    on = _render(ds, w, h, mode, _abi.rg_tiling(8, 8, share))
+    on = device_launch(ds, w, h, mode, _abi.rg_tiling(8, 8, share))
     ds.set_shadow_volume(False)
-    off = _render(ds, w, h, mode, _abi.rg_tiling(8, 8, share))
+    off = device_launch(ds, w, h, mode, _abi.rg_tiling(8, 8, share))
     ds.close()
     assert (on[2], on[3], off[2], off[3]) == (True, True, True, False)
     assert on[1] == off[1] and on[1]["shadow"] > 0, "ray counts differ"

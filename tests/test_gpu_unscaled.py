@@ -19,27 +19,26 @@ forms measured slower or no faster there).  Everything stays bit for bit:
     groups that did not ship and guard the frames around it.
 """
 import copy
-import ctypes as C
 
 import numpy as np
 import pytest
 
+import gpu_launch
+from gpu_launch import SIZES, device_launch, oracle_frame, require_device
 from raingun_amd import _abi
 from raingun_amd.color import Color
-from raingun_amd.scene import (DeviceScene, DirectionalLight, Material, Plane, Scene, SceneDesc, Sphere,
+from raingun_amd.scene import (DeviceScene, DirectionalLight, Material, Plane, Scene, Sphere,
                                SphericalLight)
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [(97, 61), (64, 40)]  # partial 8x8 tiles at the right and bottom edges; whole tiles
 LO, HI = 767, 1279            # the window's biased exponents (rg_exact.h RG_UNSCALED_EXP_LO / _HI)
 ONES = (1 << 52) - 1
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
-    lib = _abi.lib()  # raises if the HIP library is missing: no fallback
-    assert lib.rg_device_count() > 0, "no HIP device visible"
+    require_device()
 
 
 # ---------------------------------------------------------------- the primitives, both ways
@@ -128,8 +127,7 @@ def _quotient_operands(rng):
 
 @pytest.fixture(scope="module")
 def any_scene():
-    ds = DeviceScene(Scene(bodies=[Sphere((0.0, 0.0, -5.0), 1.0, Material(Color.from_str("#ffffff"), 0.5))],
-                           lights=[DirectionalLight((0.0, -1.0, -1.0), Color.from_str("#ffffff"), 1.0)]))
+    ds = DeviceScene(gpu_launch.any_scene())
     yield ds
     ds.close()
 
@@ -224,44 +222,6 @@ def _scenes(example_scenes):
     }
 
 
-_ORACLE = {}
-
-
-def _oracle(oracle_lib, key, scene, w, h):
-    """The CPU restatement's whole frame and ray counts, computed once per (scene, size) and shared."""
-    k = (key, w, h)
-    if k not in _ORACLE:
-        o_st, o_rgba, _, o_counts, _ = oracle_lib.render(SceneDesc(scene), w, h)
-        assert o_st == 0, f"the CPU restatement reports status {o_st}"
-        o_rgba.setflags(write=False)
-        _ORACLE[k] = (o_rgba, o_counts)
-    return _ORACLE[k]
-
-
-def _render(ds, w, h, mode):
-    """One device-resident launch of the whole frame -> (rgba, ray counts, ran PLAIN)."""
-    import torch
-
-    lib = _abi.lib()
-    t = _abi.rg_tiling(h, 1, 0)
-    rgba = torch.full((h, w, 4), 7, dtype=torch.uint8, device="cuda")
-    if mode == "single":
-        st = _abi.rg_stats()
-        _abi.check(lib.rg_render_tiles_async(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), None, None,
-                                             C.byref(st)))
-        counts = st.rays.as_dict()
-    else:
-        _abi.check(lib.rg_render_tiles_pipelined(ds.handle, w, h, C.byref(t), C.c_void_p(rgba.data_ptr()), None, None))
-        torch.cuda.synchronize()
-        words = (C.c_uint64 * 16)()
-        _abi.check(lib.rg_debug_counters(ds.handle, words))
-        assert words[3] == 0, "the launch reported an error"
-        counts = {"primary": words[0], "shadow": words[1], "secondary": words[2]}
-    plain = ds.last_plain()
-    torch.cuda.synchronize()
-    return rgba.cpu().numpy(), counts, plain
-
-
 NAMES = ["test1", "test1_2^-100", "test1_2^-300", "light_on_plane", "grazing", "refract", "parallel"]
 
 
@@ -270,11 +230,11 @@ NAMES = ["test1", "test1_2^-100", "test1_2^-300", "light_on_plane", "grazing", "
 @pytest.mark.parametrize("name", NAMES)
 def test_frames(oracle_lib, example_scenes, name, w, h, mode):
     scene = _scenes(example_scenes)[name]
-    o_rgba, o_counts = _oracle(oracle_lib, name, scene, w, h)
+    o_rgba, o_counts = oracle_frame(oracle_lib, name, scene, w, h)
     ds = DeviceScene(scene)
-    rgba, counts, plain = _render(ds, w, h, mode)
+    rgba, counts, plain, _ = device_launch(ds, w, h, mode)
     ds.set_exact_div(False)  # the same scene on the general kernel
-    g_rgba, g_counts, g_plain = _render(ds, w, h, mode)
+    g_rgba, g_counts, g_plain, _ = device_launch(ds, w, h, mode)
     ds.close()
     assert plain and not g_plain, f"ran the {'PLAIN' if plain else 'general'} kernel, then the {'PLAIN' if g_plain else 'general'} one"
     assert counts == o_counts and g_counts == o_counts, "ray counts differ"

@@ -2,13 +2,14 @@
 
 1. tests/native/lens_test.cpp against the shared header raingun_amd/csrc/rg_lens.h (a stand-alone program,
    AddressSanitizer + UBSan, run as a child process): the hash, hand-computed rays, "no lens".
-2. The lens reference (tests/native/lens_oracle.c through tests/lens_ref.py) tied to the camera reference,
+2. The lens reference (rgl_render of tests/native/ref_frames.c through tests/lens_ref.py) tied to the camera reference,
    and through it to the pinned oracle: with an all-zero points table and focus 1 it gives rgc_render's
    bytes and counts at (kW, kH), for the identity camera and a general pose, on test1 and synth64.
 3. rg_lens_tables (pure host code of the library): the facts of include/raingun.h.
 4. Blur grows with the aperture, on the reference alone.
 5. cli.py's --aperture / --focus, Lens, and the lens translation units in every diagnostic build.
 """
+import re
 import shutil
 import subprocess
 from pathlib import Path
@@ -19,6 +20,7 @@ import pytest
 
 import camera_ref
 import lens_ref
+import ref_lib
 from raingun_amd import _abi, aa
 from raingun_amd.camera import Camera, Lens, lens_from_flags
 from raingun_amd.cli import parse_arguments
@@ -73,12 +75,14 @@ def test_zero_points_table_is_the_camera_reference(example_scenes, name, pose):
 
 
 def test_lens_oracle_is_the_oracle_plus_one_function():
-    text = lens_ref.SRC.read_text()
+    text = ref_lib.SRC.read_text()
     assert text.count("#include") == 1 and '#include "../../oracle/raingun_oracle.c"' in text
-    assert text.count("\nint32_t rg") == 1  # one exported function
+    # one exported function per entry, and one of them the lens's
+    assert sorted(re.findall(r"^int32_t (rg\w+)\(", text, re.M)) == ["rga_render", "rgc_render", "rgl_render"]
     for p in (REPO / "raingun_amd").rglob("*"):  # nothing of the product includes or loads it
         if p.is_file() and p.suffix in (".py", ".h", ".hip", ".cpp", ".c") or p.name == "Makefile":
-            assert "lens_oracle" not in p.read_text(errors="replace"), p
+            text = p.read_text(errors="replace")
+            assert "ref_frames" not in text and "ref_lib" not in text and "lens_oracle" not in text, p
 
 
 # ---------------------------------------------------------------- 3. rg_lens_tables
