@@ -172,6 +172,17 @@ rg_status rg_debug_set_shadow_volume(rg_scene *scene, int32_t on);
 rg_status rg_debug_shadow_volume_info(const rg_scene *scene, rg_shadow_volume_info *info);
 rg_status rg_debug_last_shadow_volume(const rg_scene *scene, int32_t *used);
 
+/* First-hit tiles of the PLAIN light kernels: an 8x8 tile whose 64 primary rays all end at a miss, a
+ * diffuse hit, or a reflecting hit at the depth limit needs no recursion state, and its wave shades
+ * and stores it in one straight line (primary hit, shadow batch, shade, store) instead of three trips
+ * round the general state machine; any other tile, and any tile with a shadow ray that could see a NaN
+ * distance, goes the general way.  rg_debug_set_first_hit_tiles(0): no tile of the scene's launches
+ * takes the path (1, the default: the wave's vote decides).  Results are identical either way.
+ * rg_debug_last_first_hit_tiles: *tiles = the tiles of the scene's latest render launch that finished
+ * on the path (0 for any other kernel). */
+rg_status rg_debug_set_first_hit_tiles(rg_scene *scene, int32_t on);
+rg_status rg_debug_last_first_hit_tiles(const rg_scene *scene, uint64_t *tiles);
+
 /* The PLAIN light kernels compute the camera ray's two quotients from host reciprocals and its
  * length without range scaling, after the launcher has checked the frame size column by column and
  * row by row and bounded the field of view.  rg_debug_set_exact_div(0): the scene's launches behave

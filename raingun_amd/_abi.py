@@ -177,6 +177,7 @@ DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "
                  "rg_debug_counter_words", "rg_debug_set_aa_band_rows",
                  "rg_debug_set_aa_adaptive_timing", "rg_debug_aa_adaptive_info", "rg_debug_last_plain",
                  "rg_debug_set_shadow_volume", "rg_debug_shadow_volume_info", "rg_debug_last_shadow_volume",
+                 "rg_debug_set_first_hit_tiles", "rg_debug_last_first_hit_tiles",
                  "rg_debug_set_exact_div", "rg_debug_camera_check", "rg_debug_unscaled_check")
 # include/raingun_frames.h
 FRAMES_SYMBOLS = ("rg_frames_create", "rg_frames_destroy", "rg_frames_step", "rg_frames_flush", "rg_frames_image",
@@ -281,6 +282,11 @@ def _declare(lib: C.CDLL) -> None:
         lib.rg_debug_shadow_volume_info.argtypes = [C.c_void_p, P(rg_shadow_volume_info)]
         lib.rg_debug_last_shadow_volume.restype = C.c_int32
         lib.rg_debug_last_shadow_volume.argtypes = [C.c_void_p, P(C.c_int32)]
+    if hasattr(lib, "rg_debug_set_first_hit_tiles"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
+        lib.rg_debug_set_first_hit_tiles.restype = C.c_int32
+        lib.rg_debug_set_first_hit_tiles.argtypes = [C.c_void_p, C.c_int32]
+        lib.rg_debug_last_first_hit_tiles.restype = C.c_int32
+        lib.rg_debug_last_first_hit_tiles.argtypes = [C.c_void_p, P(C.c_uint64)]
     if hasattr(lib, "rg_debug_set_exact_div"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
         lib.rg_debug_set_exact_div.restype = C.c_int32
         lib.rg_debug_set_exact_div.argtypes = [C.c_void_p, C.c_int32]

@@ -568,6 +568,17 @@ rg_status rg_debug_last_shadow_volume(const rg_scene *s, int32_t *used) {
     return RG_OK;
 }
 
+rg_status rg_debug_set_first_hit_tiles(rg_scene *s, int32_t on) {
+    if (!s || (on != 0 && on != 1)) return RG_ERR_INVALID_ARGUMENT;
+    s->first_hit_enabled = on != 0;
+    return RG_OK;
+}
+
+rg_status rg_debug_last_first_hit_tiles(const rg_scene *s, uint64_t *tiles) {
+    if (!s || !tiles || !s->last) return RG_ERR_INVALID_ARGUMENT;
+    return rg_debug_counter_words(s, RG_FIRST_HIT_WORD, 1, tiles);
+}
+
 rg_status rg_debug_set_exact_div(rg_scene *s, int32_t enable) {
     if (!s || (enable != 0 && enable != 1)) return RG_ERR_INVALID_ARGUMENT;
     s->exact_div = enable != 0;

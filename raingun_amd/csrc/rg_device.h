@@ -255,7 +255,13 @@ struct RgKernelArgs {
     float shvol_inv, shvol_off;
     // the struct grows by 32 bytes, so the arguments that follow it in other kernels (rg_trace_kernel,
     // rg_aov_kernel) keep their 16-byte phase and those kernels their code (profiles/shvol/kernel_isa_diff.txt)
-    uint32_t shvol_pad[3];
+    // first_hit_off, in the padding's first word so that no offset moves: nonzero = no tile takes the PLAIN
+    // light kernels' first-hit path (rg_render_kernel.h; rg_debug_set_first_hit_tiles(0)) --
+    // its vote fails in every wave
+    union {
+        uint32_t shvol_pad[3];
+        uint32_t first_hit_off;
+    };
     // The launch's thin lens (rg_lens.h; rg_scene_set_lens), by value: lens != 0 selects the lens family
     // of rg_render_kernel (rg_render_cfg.h RG_MAXD_LENS; a band of a supersampled frame with lens_k x lens_k
     // samples per pixel, rg_aa.hip), whose primary rays leave cam_eye + O for the point of the plane in
@@ -325,6 +331,12 @@ __host__ __device__ inline unsigned long long rg_tile_count(const RgKernelArgs &
 #ifndef RG_PLAIN_SHVOL_PLANES
 #define RG_PLAIN_SHVOL_PLANES 1
 #endif
+// The PLAIN light kernels' straight-line path for tiles whose primary rays all end at a miss or a hit
+// that needs no secondary ray (rg_render_kernel.h; 0: every tile through the state
+// machine, the parent's code, for A/B builds).
+#ifndef RG_PLAIN_FIRST_HIT
+#define RG_PLAIN_FIRST_HIT 1
+#endif
 #ifndef RG_HEAVY_WPS
 #define RG_HEAVY_WPS 3            // heavy path: waves per SIMD (block = 256 * WPS threads; 168 VGPRs)
 #endif
@@ -347,6 +359,7 @@ __host__ __device__ __forceinline__ bool rg_heavy_path(const RgKernelArgs &a) {
 
 #define RG_COUNTER_WORDS (16 + 16 * 16 + 16)  // stats + 16 queue heads, 128 B apart + the finished-wave count
 #define RG_DONE_WORD (16 + 16 * 16)            // waves of the launch that finished (RgKernelArgs::snap_out)
+#define RG_FIRST_HIT_WORD (RG_DONE_WORD + 1)   // tiles of the launch that finished on the PLAIN kernels' first-hit path
 
 // counters[3] holds ~((pixel << 8) | -status) of the lowest erroring pixel
 // (atomicMax of the complement); 0 = no error, so one memset resets all four.

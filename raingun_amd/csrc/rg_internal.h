@@ -198,6 +198,7 @@ struct rg_scene {
     bool lbuf_enabled = true;       // rg_debug_set_lightbuf
     uint32_t *shvol = nullptr;      // shadow mask volume of the PLAIN light kernels (rg_shadow_vol.cpp), null: none
     bool shvol_enabled = true;      // rg_debug_set_shadow_volume
+    bool first_hit_enabled = true;  // rg_debug_set_first_hit_tiles
     rg_shadow_volume_info shvol_info{};  // g, bytes, build time, set share; inv / off below (rg_shvol_cell's constants)
     float shvol_inv = 0.0f, shvol_off = 0.0f;
     bool exact_div = true;          // rg_debug_set_exact_div: 0 = launches behave as if the quotient sweep had failed

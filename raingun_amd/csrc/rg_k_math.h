@@ -169,7 +169,7 @@ enum : int {
     RGR_UNWIND_STEP, RGR_TILE_FETCH, RGR_Q_CLOSEST, RGR_Q_SHADOW, RGR_SH_GROUP, RGR_SH_TAIL, RGR_SH_PLANE,
     RGR_SH_PLANE_DIV, RGR_QC_GROUP, RGR_QC_TAIL, RGR_QC_PLANE, RGR_PRIM_GROUP, RGR_PRIM_PLANE, RGR_DISK, RGR_BOX,
     RGR_PUSH_REFL, RGR_PUSH_REFR, RGR_UNWIND_REFRT, RGR_ERROR, RGR_SH_PAIR, RGR_PRIM_PAIR, RGR_QC_PAIR,
-    RGR_WALK, RGR_WALK_LEAF, RGR_LB_SHADOW, RGR_COUNT
+    RGR_WALK, RGR_WALK_LEAF, RGR_LB_SHADOW, RGR_FIRST_HIT, RGR_COUNT
 };
 static_assert(RG_REGION_BASE + 2 * RGR_COUNT <= 16 + 16 * 15, "region counters stay below tile-queue head 15");
 #ifdef RG_REGION_STATS

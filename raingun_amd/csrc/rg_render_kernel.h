@@ -279,6 +279,7 @@ void rg_render_kernel(RgKernelArgs a) {
         nring = 0;
     };
     uint32_t n_prim = 0, n_shadow = 0, n_sec = 0;
+    [[maybe_unused]] uint32_t n_first_hit = 0;  // (wave-uniform) tiles the wave finished on the first-hit path
     FrameStack<K::array_frames> stk;  // K::global_frames: field-major frames in a global buffer, no scratch array
     stk.init(a);
 
@@ -883,6 +884,107 @@ void rg_render_kernel(RgKernelArgs a) {
                     qdepth = 0;
                     task = -1;
                 }
+                if constexpr (PLAIN && RG_PLAIN_FIRST_HIT != 0) {
+                    // First-hit tiles.  Every lane of the wave is here, at depth 0 with a fresh
+                    // primary result or without a pixel.  A tile whose primary rays all end at a miss, a diffuse
+                    // hit or a reflecting hit at the depth limit needs no frame, no mode and no parked factors:
+                    // the wave shades it here in one straight line -- the general block's functions in the general
+                    // block's order (rendering.rs:80-91, 141-170), so the pixels are the same bits -- and takes
+                    // the next tile.  Nothing of the lane state is consumed before the wave commits: a failed
+                    // vote, or a batch that could see a NaN distance, leaves the tile to the loop as it stood.
+                    const bool hit = alive && c.id >= 0;
+                    const int surf = hit ? T.mats[c.id].surface : RG_SURFACE_DIFFUSE;
+                    const bool simple = !alive || (!c.nan && (surf == RG_SURFACE_DIFFUSE ||
+                                                              (surf == RG_SURFACE_REFLECTING && 1 >= max_depth)));
+                    if (!a.first_hit_off && !__any(!simple)) {  // (wave-uniform) rg_debug_set_first_hit_tiles(0): no tile
+                        RG_REGION(RGR_FIRST_HIT);
+                        // (the batch and its origin in the loop's own sb and q.o, which hold nothing at a tile's
+                        // start: no second copy in registers.  q.o is the primary ray's origin, 0, until then.)
+                        static_assert(!K::camera, "the primary rays of a PLAIN kernel leave the origin");
+                        float pp[LB], lin[LB];
+                        C3 bc = c3(0.0f, 0.0f, 0.0f);
+                        float refl = 0.0f, rr = 0.0f;
+                        [[maybe_unused]] uint32_t fw = 0u;
+                        bool bail = false;
+#pragma unroll
+                        for (int l = 0; l < LB; ++l) pp[l] = lin[l] = 0.0f;
+                        if (hit) {
+                            const RgBodyDev b = T.bodies[c.id];
+                            const RgMatDev m = T.mats[c.id];
+                            const V3 h = add(q.o, scl(q.d, c.t));
+                            V3 n;
+                            if (!surface_normal(b, h, n)) bail = true;  // the general block reports it
+                            const bool textured = m.coloration != RG_COLORATION_COLOR;
+                            uint32_t texel = 0u;
+                            if (textured) texel = texel_fetch_plain(T.texs, PT, m, b, c.id, h);
+                            else bc = c3(m.color[0], m.color[1], m.color[2]);
+                            refl = m.albedo_pi;      // rendering.rs:164
+                            rr = m.reflectivity;     // read by a reflecting hit only (kind 1)
+                            q.o = add(h, scl(n, SHADOW_BIAS));  // rendering.rs:148
+                            if constexpr (SHV) {
+                                fw = RG_SHVOL_ALL;
+                                if (a.shvol) {  // (wave-uniform)
+                                    const int cell = rg_shvol_cell((float)q.o.x, (float)q.o.y, (float)q.o.z, a.shvol_inv,
+                                                                   a.shvol_off, (int)a.shvol_g);
+                                    const uint32_t w = a.shvol[cell >= 0 ? cell : 0];
+                                    if (cell >= 0) fw = w;
+                                }
+                            }
+#pragma unroll
+                            for (int l = 0; l < LB; ++l) {
+                                const RgLightDev L = T.lights[l];
+                                light_dir_dist<UL>(L, h, sb.d[l], sb.ld[l]);
+                                pp[l] = fmaxf((float)dot(n, sb.d[l]), 0.0f);  // rendering.rs:161-162
+                                lin[l] = light_intensity(L, h);               // pure; used if lit
+                                bail |= ray_exotic(q.o, sb.d[l]);
+                            }
+                            if (textured) bc = texel_color(texel);
+                        }
+                        if (__any(bail)) {
+                            q.o = v3(0.0, 0.0, 0.0);  // the primary ray again; sb is set up anew before it is read
+                        } else {  // commit: from here the tile is this path's
+                            // (the primary ray and its result are spent: nothing of them lives through the walk)
+                            q.d = v3(0.0, 0.0, 0.0);
+                            closest_init(c);
+                            uint32_t focc = 0u;
+                            [[maybe_unused]] uint32_t smask = ~0u, pmask = ~0u;
+                            bool walk = true;  // (wave-uniform)
+                            if constexpr (SHV) {
+                                if (a.shvol) {  // (a volume's scene has no body past the masks' bits: rg_shadow_vol.h)
+                                    const uint32_t wm = wave_or(hit ? fw : 0u);
+                                    smask = wm & 0xFFFFu;
+                                    pmask = wm >> 16;
+                                    walk = wm != 0u;
+                                }
+                            }
+                            C3 fret = def;  // rendering.rs:76-77
+                            if (hit) {
+                                if (walk) trace_shadow<LB, PLAIN, SHV>(a, src, q.o, sb, (1u << LB) - 1u, focc, smask, pmask);
+                                n_shadow += (uint32_t)LB;
+                                // shade_diffuse accumulation (rendering.rs:141-170), in light order
+                                C3 acc = c3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+                                for (int l = 0; l < LB; ++l) {
+                                    const RgLightDev L = T.lights[l];
+                                    const float inten = !((focc >> l) & 1u) ? lin[l] : 0.0f;
+                                    const float power = pp[l] * inten;
+                                    const C3 lc = cscl(cscl(c3(L.color[0], L.color[1], L.color[2]), power), refl);
+                                    acc = cadd(acc, cmul(bc, lc));
+                                }
+                                const C3 dcol = cclamp(acc);
+                                // Diffuse, or Reflecting with its ray at depth >= max (rendering.rs:86-91, 123-124)
+                                fret = surf == RG_SURFACE_DIFFUSE ? dcol : cadd(cscl(dcol, 1.0f - rr), cscl(def, rr));
+                            }
+                            if (alive) {
+                                a.rgba[oidx] = f32_to_u8(fret.r * 255.0f) | (f32_to_u8(fret.g * 255.0f) << 8) |
+                                               (f32_to_u8(fret.b * 255.0f) << 16) | 0xFF000000u;
+                            }
+                            mode = MODE_DONE;
+                            have_result = false;
+                            ++n_first_hit;
+                        }
+                    }
+                }
                 continue;
             }
         }
@@ -1107,6 +1209,9 @@ void rg_render_kernel(RgKernelArgs a) {
         if (p64) atomicAdd(&a.counters[0], p64);
         if (s64) atomicAdd(&a.counters[1], s64);
         if (q64) atomicAdd(&a.counters[2], q64);
+        if constexpr (PLAIN && RG_PLAIN_FIRST_HIT != 0) {
+            if (n_first_hit) atomicAdd(&a.counters[RG_FIRST_HIT_WORD], (unsigned long long)n_first_hit);
+        }
         if (a.snap_out) {
             // the last wave to finish hands the statistics words to the host itself (the copy
             // after the kernel would be a blit kernel of its own on the stream): this wave's

@@ -250,6 +250,7 @@ RgKernelArgs rg_make_args(const rg_scene *s) {
     a.shvol_g = shvol ? (uint32_t)s->shvol_info.g : 0u;
     a.shvol_inv = s->shvol_inv;
     a.shvol_off = s->shvol_off;
+    a.first_hit_off = s->first_hit_enabled ? 0u : 1u;  // rg_debug_set_first_hit_tiles(0)
     return a;
 }
 
@@ -345,6 +346,7 @@ void rg_sync_settings(rg_scene *dst, const rg_scene *src) {
     dst->bvh_enabled = src->bvh_enabled;
     dst->lbuf_enabled = src->lbuf_enabled;
     dst->shvol_enabled = src->shvol_enabled;
+    dst->first_hit_enabled = src->first_hit_enabled;
     dst->exact_div = src->exact_div;
     dst->has_camera = src->has_camera;
     dst->camera = src->camera;

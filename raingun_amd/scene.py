@@ -341,6 +341,17 @@ class DeviceScene:
         _abi.check(_abi.lib().rg_debug_last_shadow_volume(self.handle, C.byref(used)))
         return used.value == 1
 
+    def set_first_hit_tiles(self, on: bool) -> None:
+        """False: no tile takes the PLAIN light kernels' first-hit path; every tile goes through the
+        general state machine (include/raingun_debug.h rg_debug_set_first_hit_tiles)."""
+        _abi.check(_abi.lib().rg_debug_set_first_hit_tiles(self.handle, 1 if on else 0))
+
+    def last_first_hit_tiles(self) -> int:
+        """Tiles of the latest render launch that finished on the PLAIN light kernels' first-hit path."""
+        tiles = C.c_uint64(0)
+        _abi.check(_abi.lib().rg_debug_last_first_hit_tiles(self.handle, C.byref(tiles)))
+        return int(tiles.value)
+
     def set_exact_div(self, enable: bool) -> None:
         """False: launches behave as if the PLAIN kernels' camera-quotient check had failed, so they run
         the general kernel (include/raingun_debug.h rg_debug_set_exact_div)."""
