@@ -25,3 +25,28 @@ def test_shape():
     kinds = [b.material.surface for b in s.bodies if isinstance(b, Sphere)]
     assert 0.55 < kinds.count("Diffuse") / 4096 < 0.65
     assert 0.12 < kinds.count("Refractive") / 4096 < 0.18
+
+
+def test_mixed_scene_tables_keep_the_yaml_order():
+    """tests/mixed_scenes.py: the flat descriptor that rg_scene_create groups by kind holds the shuffled mix of
+    kinds body for body, in YAML order.  (The grouped tables' ids live behind the scene handle; the GPU module's
+    `body` layer and rg_trace tests check that they map back to these indices.)"""
+    from mixed_scenes import config_scene
+    from raingun_amd import _abi
+    from raingun_amd.scene import AABB, Disk, SceneDesc, Texture
+
+    s = config_scene("many")
+    desc = SceneDesc(s)
+    assert desc.desc.n_bodies == len(s.bodies) == 98 and desc.desc.n_textures == 2
+    kind = {Sphere: _abi.BODY_SPHERE, Plane: _abi.BODY_PLANE, Disk: _abi.BODY_DISK, AABB: _abi.BODY_AABB}
+    want = [kind[type(b)] for b in s.bodies]
+    assert [desc.desc.bodies[i].kind for i in range(len(want))] == want
+    assert len({k for k in want[:8]}) >= 3, "the first bodies are of one kind: no interleaving"
+    for i, b in enumerate(s.bodies):
+        p = list(desc.desc.bodies[i].p)
+        head = [*b.center, b.radius] if isinstance(b, Sphere) else [*b.origin, *b.normal] if isinstance(b, Plane) \
+            else [*b.origin, *b.normal, b.radius] if isinstance(b, Disk) else [*b.bounds[0], *b.bounds[1]]
+        assert p[:len(head)] == head, i
+        m = desc.desc.bodies[i].material
+        assert (m.coloration == _abi.COLORATION_TEXTURE) == isinstance(b.material.coloration, Texture), i
+        assert (m.texture >= 0) == isinstance(b.material.coloration, Texture), i
