@@ -453,6 +453,47 @@ rg_status rg_scene_set_lens(rg_scene *scene, const rg_lens *lens);
  * `points`. */
 rg_status rg_lens_tables(uint32_t samples, double *points, double *rotations);
 
+/* Area lights: soft shadows for the supersampled frames.  A spherical light l gets a radius radii[l] >= 0
+ * in world units; a directional light has no position and stays hard: its radius must be 0.
+ * The radii apply to the samples x samples rays per pixel of rg_render_image_aa and rg_render_aa_async for
+ * samples >= 2, and to nothing else: with samples == 1, or with every radius 0, those two calls launch the
+ * kernels and give the bytes they give today.  Deterministic, no random numbers: with k = samples, (X, Y) a
+ * pixel of the kW x kH sample frame (Y the row of the whole frame), l the light's index in the scene's
+ * order and v its position -- u32 wrap-around, then f64, unfused, in this order:
+ *   s = (Y % k) * k + (X % k)                          the sample
+ *   n = (Y / k) * W + (X / k)                          the output pixel
+ *   g = lowbias32(n ^ ((l + 1) * 0x9e3779b9))          the hash of rg_lens above
+ *   j = (s + (g >> 6)) % (k * k)                       this pixel's and light's shift through the points
+ *   (c, e) = rotations[g & 63]                         rg_lens_tables' 64 turns, here about world z
+ *   (px, py, pz) = sphere_points_k[j]                  rg_area_tables'
+ *   qx = c * px - e * py;  qy = e * px + c * py;  qz = pz
+ *   position.c = v.c + radii[l] * q.c                  for every spherical light, radius 0 included
+ * Everything the reference does with the light's position (lights.rs:36-58: direction_from, distance, the
+ * intensity's falloff) uses `position` instead, for every hit of that sample's whole ray tree: primary,
+ * reflected and transmitted hits alike.  The samples of a pixel see k^2 points spread evenly over the
+ * light's sphere, so a shadow's edge resolves into a penumbra.  Area lights combine with the camera and
+ * with the lens.
+ *
+ * rg_scene_set_light_radii sets the radii of every later rg_render_image_aa / rg_render_aa_async of `scene`;
+ * NULL: point lights again, and with them (as with every radius 0) exactly the kernels those calls launched
+ * before.  n must be the scene's light count.  Unlike the camera and the lens the radii are one per light
+ * and live in a table on the device, which launches read by reference: the call BLOCKS until the scene's
+ * device is idle before it rewrites that table, and launches enqueued later see the new radii.
+ * rg_render_multi's replicas copy the radii.  The entry points that trace one ray per pixel ignore them:
+ * rg_render_image, rg_render_tiles / _async / _pipelined, rg_render_stream, rg_render_multi, rg_frames_*,
+ * rg_render_aov / _async and rg_trace.  While any radius is > 0, rg_render_image_aa_adaptive and
+ * rg_render_aa_adaptive return RG_ERR_INVALID_ARGUMENT: their edge mask comes from a hard-shadow frame and
+ * says nothing about penumbrae.  Ray counts, error_pixel and status codes of the two AA calls keep their
+ * meaning.  RG_ERR_INVALID_ARGUMENT for a null scene, n other than the light count, a non-finite or
+ * negative radius, or a non-zero radius on a directional light (the scene keeps the radii it had). */
+rg_status rg_scene_set_light_radii(rg_scene *scene, const double *radii, uint32_t n);
+
+/* The area lights' points, pure host code.  points: 3 * samples^2 doubles, uniform on the unit sphere: cell
+ * (i, j) of the samples x samples grid, at index j * samples + i, with u = (i + 0.5) / samples,
+ * v = (j + 0.5) / samples:  z = 1 - 2u, rho = sqrt(1 - z z), phi = 2 pi v, point = (rho cos phi, rho sin phi, z).
+ * RG_ERR_INVALID_ARGUMENT for samples outside 1 .. 8 or a null `points`. */
+rg_status rg_area_tables(uint32_t samples, double *points);
+
 #ifdef __cplusplus
 }
 #endif

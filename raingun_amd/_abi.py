@@ -168,6 +168,8 @@ EXPORTED_SYMBOLS = (
     "rg_render_aov_async",
     "rg_scene_set_lens",
     "rg_lens_tables",
+    "rg_scene_set_light_radii",
+    "rg_area_tables",
 )
 # include/raingun_debug.h
 DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "rg_debug_counters",
@@ -218,6 +220,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.rg_scene_set_lens.argtypes = [C.c_void_p, P(rg_lens)]
     lib.rg_lens_tables.restype = C.c_int32
     lib.rg_lens_tables.argtypes = [C.c_uint32, P(C.c_double), P(C.c_double)]
+    lib.rg_scene_set_light_radii.restype = C.c_int32
+    lib.rg_scene_set_light_radii.argtypes = [C.c_void_p, P(C.c_double), C.c_uint32]
+    lib.rg_area_tables.restype = C.c_int32
+    lib.rg_area_tables.argtypes = [C.c_uint32, P(C.c_double)]
     lib.rg_render_image.restype = C.c_int32
     lib.rg_render_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, P(rg_stats)]
     lib.rg_render_tiles_async.restype = C.c_int32

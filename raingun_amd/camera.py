@@ -114,6 +114,33 @@ def lens_from_flags(aperture, focus, samples: int, adaptive) -> "Optional[Lens]"
     return lens
 
 
+def light_radii_from_flags(text, samples: int, adaptive) -> "Optional[Tuple[float, ...]]":
+    """The numbers of the CLI's --light-radius (a string or None) as given: one for every spherical light, or a
+    comma list with one entry per light of the scene in YAML order (spread_light_radii, once the scene is
+    read); None without the flag.  ValueError unless each is finite and >= 0, with --samples >= 2 and no
+    --adaptive."""
+    if text is None:
+        return None
+    radii = tuple(float(p) for p in str(text).split(","))  # float('x') raises ValueError
+    if not all(math.isfinite(r) and r >= 0.0 for r in radii):
+        raise ValueError("a light radius is a finite number >= 0")
+    if samples < 2:
+        raise ValueError("area lights need --samples 2 or more")
+    if adaptive is not None:
+        raise ValueError("area lights cannot be combined with --adaptive")
+    return radii
+
+
+def spread_light_radii(radii: Sequence[float], spherical: Sequence[bool]) -> Tuple[float, ...]:
+    """--light-radius for a scene whose lights are spherical[l]: one number goes to every spherical light (a
+    directional one gets 0), a list is one entry per light.  ValueError for a list of another length."""
+    if len(radii) == 1:
+        return tuple(radii[0] if s else 0.0 for s in spherical)
+    if len(radii) != len(spherical):
+        raise ValueError(f"--light-radius lists {len(radii)} radii, the scene has {len(spherical)} lights")
+    return tuple(radii)
+
+
 def parse_triple(text: str) -> Vec:
     """'X,Y,Z' -> three floats (the CLI's --eye / --look-at / --up); ValueError otherwise."""
     parts = text.split(",")

@@ -2,7 +2,7 @@
 
     python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
                               [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D]
-                              [--aov LAYERS] [-o FILE] FILE
+                              [--light-radius R[,R...]] [--aov LAYERS] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
@@ -24,6 +24,11 @@ front of the camera, focused on the plane D forward lengths away
 (rg_scene_set_lens): depth of field from the N x N rays of --samples, so they
 need --samples 2 or more and refuse --adaptive, and go together; they combine
 with the camera and the size flags.
+`--light-radius R` (not in the reference) gives every spherical light of the
+scene the radius R in world units (rg_scene_set_light_radii): soft shadows from
+the N x N rays of --samples, so it needs --samples 2 or more and refuses
+--adaptive; a comma list gives one radius per light in YAML order (0 for a
+directional light).  It combines with the camera and the lens.
 `--aov LAYERS` (not in the reference; a comma list of body, depth, normal, uv,
 albedo, or `all`) also writes, next to `-o out.png`, `out.<layer>.png` for each
 named layer: what lies under each pixel (rg_render_aov), as the pictures of
@@ -47,7 +52,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import aov
-from .camera import Camera, Lens, camera_from_flags, lens_from_flags, parse_triple
+from .camera import (Camera, Lens, camera_from_flags, lens_from_flags, light_radii_from_flags, parse_triple,
+                     spread_light_radii)
 
 
 @dataclass
@@ -59,6 +65,7 @@ class RenderOptions:          # render.rs:32-46
     adaptive: Optional[int] = None  # contrast threshold of adaptive anti-aliasing (--adaptive)
     camera: Optional[Camera] = None  # --eye / --look-at / --up (not in the reference)
     lens: Optional[Lens] = None      # --aperture / --focus (not in the reference)
+    light_radii: Optional[tuple] = None  # --light-radius as given: one number or one per light (not in the reference)
     aov: tuple = ()           # layers of --aov, in aov.LAYERS order (not in the reference)
 
 
@@ -97,6 +104,8 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("--up", metavar="X,Y,Z", help="Up hint of --look-at (default 0,1,0).")
     p.add_argument("--aperture", metavar="R", help="Lens radius in world units (with --focus and --samples >= 2).")
     p.add_argument("--focus", metavar="D", help="Distance of the plane in focus, in lengths of the forward vector.")
+    p.add_argument("--light-radius", dest="light_radius", metavar="R[,R...]",
+                   help="Radius of every spherical light in world units, or one per light (with --samples >= 2).")
     p.add_argument("--aov", metavar="LAYERS",
                    help="Also write FILENAME.<layer>.png for each of a comma list of body, depth, normal, uv, "
                         "albedo (or all).")
@@ -119,6 +128,10 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
         o.lens = lens_from_flags(ns.aperture, ns.focus, o.samples, o.adaptive)
     except ValueError as e:
         raise SystemExit(f"Could not build the lens: {e}") from None
+    try:
+        o.light_radii = light_radii_from_flags(ns.light_radius, o.samples, o.adaptive)
+    except ValueError as e:
+        raise SystemExit(f"Could not build the area lights: {e}") from None
     if ns.aov is not None:
         try:
             o.aov = aov.parse_layers(ns.aov)
@@ -229,6 +242,13 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
     ds = DeviceScene(scene, device=ns.gpu)
     ds.set_camera(opts.camera)
     ds.set_lens(opts.lens)
+    if opts.light_radii is not None:
+        from .scene import SphericalLight
+
+        try:
+            ds.set_light_radii(spread_light_radii(opts.light_radii, [isinstance(l, SphericalLight) for l in scene.lights]))
+        except ValueError as e:
+            raise SystemExit(f"Could not build the area lights: {e}") from None
     t0 = time.perf_counter()                     # render.rs:54-56
     if opts.samples > 1 and opts.adaptive is not None:
         img = ds.render_image_aa_adaptive(opts.width, opts.height, opts.samples, opts.adaptive)

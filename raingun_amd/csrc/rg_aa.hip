@@ -26,6 +26,7 @@
 #include "rg_device.h"
 #include "rg_internal.h"
 #include "rg_launchers.h"
+#include "rg_area.h"
 #include "rg_lens.h"
 #include "rg_sample_tiles.h"
 
@@ -84,7 +85,8 @@ rg_status ensure_aa_res(const rg_scene *s, const aa_plan &p) {
             return st;
     // a frame through the scene's lens: the tables, once per scene (a blocking copy: they are complete
     // before the first launch that reads them is enqueued, and nothing writes them again)
-    if (rg_lens_active(s->lens.aperture, p.k) && !r.d_lens) {
+    // (a frame with area lights reads the turns of the same tables)
+    if ((rg_lens_active(s->lens.aperture, p.k) || rg_area_active(s->area_any, p.k)) && !r.d_lens) {
         double table[RG_LENS_TABLE_DOUBLES];
         rg_lens_make_tables(table);
         void *d = nullptr;
@@ -97,6 +99,10 @@ rg_status ensure_aa_res(const rg_scene *s, const aa_plan &p) {
             return RG_ERR_DEVICE;
         }
         r.d_lens = static_cast<double *>(d);
+    }
+    // a replica's area table, which rg_scene_set_light_radii of the scene it copies did not write
+    if (rg_area_active(s->area_any, p.k) && (s->area_stale || !s->d_area)) {
+        if ((st = rg_area_upload(const_cast<rg_scene *>(s))) != RG_OK) return st;
     }
     return RG_OK;
 }
@@ -118,6 +124,7 @@ rg_status enqueue_bands(const rg_scene *s, const aa_plan &p, uint8_t *out_rgba, 
         d.snap = snaps ? r.h_snap + 4 * (size_t)b : nullptr;
         d.lens_k = p.k;  // the samples of a pixel leave the scene's lens, if it has one (k >= 2)
         d.lens_tab = r.d_lens;
+        d.area_tab = s->d_area;  // ... and see its lights with their radii, if any has one
         const rg_status st = rg_launch_tiles(s, d);
         if (st != RG_OK) return st;
         const size_t off = (size_t)b * p.band_rows * p.width;  // the last band is partial: only rows below host_rows
@@ -313,6 +320,8 @@ rg_status adaptive_check(const void *scene, uint32_t W, uint32_t H, uint32_t k, 
     if (v != RG_OK) return v;
     // no adaptive form through a lens: the edge mask comes from a pinhole frame and says nothing about defocus
     if (static_cast<const rg_scene *>(scene)->lens.aperture > 0.0) return RG_ERR_INVALID_ARGUMENT;
+    // nor with area lights: the mask comes from a hard-shadow frame and says nothing about penumbrae
+    if (static_cast<const rg_scene *>(scene)->area_any) return RG_ERR_INVALID_ARGUMENT;
     return threshold > 256 ? RG_ERR_INVALID_ARGUMENT : RG_OK;
 }
 

@@ -273,7 +273,17 @@ struct RgKernelArgs {
     uint32_t lens, lens_k;
     double lens_focus, lens_r[3], lens_u[3];
     const double *lens_tab;
-    uint32_t lens_pad[2];
+    // The launch's area lights (rg_area.h; rg_scene_set_light_radii), in the lens's padding so that no offset
+    // moves and the struct keeps its size: area_tab, the scene's device table (every k's points, then the
+    // radii, one per light), is at once the flag -- non-null selects the area family of rg_render_kernel
+    // (rg_render_cfg.h RG_MAXD_AREA; a band of a supersampled frame with lens_k x lens_k samples per pixel),
+    // whose every use of a spherical light's position takes the sample's point of the light's sphere, turned
+    // by lens_tab + 2 * RG_LENS_POINTS.  Such a launch has camera != 0 (the identity camera where the scene
+    // has none), takes the lens ray where lens != 0, and has no light buffers (lbuf null, n_lbuf 0, lb_cam -1).
+    union {
+        uint32_t lens_pad[2];
+        const double *area_tab;
+    };
 };
 
 __host__ __device__ inline uint32_t rg_tile_w(const RgKernelArgs &a) { return 1u << a.tile_wlog; }

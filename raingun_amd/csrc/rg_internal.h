@@ -209,6 +209,14 @@ struct rg_scene {
     // rg_scene_set_lens: host state like the camera, read when a band of a supersampled frame is enqueued
     // and passed by value (RgKernelArgs::lens ..); aperture == 0: no lens
     rg_lens lens{0.0, 1.0};
+    // rg_scene_set_light_radii (rg_area.h): one radius per light (empty: point lights), whether any is > 0, and
+    // the device table a band of a supersampled frame reads them from (RgKernelArgs::area_tab: every k's points,
+    // then the radii).  Unlike the camera and the lens the radii are as many as the scene has lights, so they
+    // travel by reference: the table is rewritten only with the device idle (rg_area_upload).  area_stale: the
+    // host radii are newer than the table (a replica, whose table is made when a frame first needs it).
+    std::vector<double> light_radii;
+    bool area_any = false, area_stale = false;
+    double *d_area = nullptr;
     float bvh_obound = 0.0f;
     double bvh_rbound = 0.0, bvh_margin = 0.0, bvh_extent = 0.0;
     rg_bvh_info bvh_info{};
@@ -289,6 +297,9 @@ struct rg_launch_desc {
     // device tables (rg_aa_res::d_lens)
     uint32_t lens_k = 0;
     const double *lens_tab = nullptr;
+    // ... and the scene's area lights if any light has a radius (rg_area.h rg_area_active): the scene's device
+    // table (rg_scene::d_area); such a launch reads the turns of lens_tab too
+    const double *area_tab = nullptr;
 };
 
 // Enqueue one tiled render on d.stream (the body of rg_render_tiles_async).
@@ -311,6 +322,9 @@ void *rg_host_device_ptr(void *p, size_t bytes);
 rg_status rg_scene_replica(const rg_scene *src, int32_t device, rg_scene **out);
 void rg_scene_free(rg_scene *s);
 void rg_sync_settings(rg_scene *dst, const rg_scene *src);  // depth, path, BVH, lane depth, tile order
+// The scene's area table (rg_area.h: the points, then s->light_radii) onto its device, made on first use.
+// Blocking: it waits for the device to go idle before it writes, so no launch in flight reads a torn table.
+rg_status rg_area_upload(rg_scene *s);
 
 // rg_multi.hip: free the scene's multi-GPU resources (replicas, communicators).
 void rg_multi_release(const rg_scene *s);

@@ -15,7 +15,9 @@ namespace rgk {
 // the block (its pixel finished, or its wave out of tiles) may take it, trace
 // the subtree with the same state machine and hand the colour back; if nobody
 // took it by the time the owner needs it, the owner reclaims it and traces it
-// itself.  A subtree's colour is a function of its ray only, and the owner
+// itself.  A subtree's colour is a function of its ray only (in the area
+// family, rg_area.h: of its ray and its owner's pixel, which pix carries to
+// whoever traces it), and the owner
 // combines it with exactly the expression of FR_REFR_R, so results are
 // identical whoever traces it.  This splits the long ray trees of
 // refractive pixels (the slowest tiles, which bound a frame's makespan)
@@ -30,7 +32,7 @@ struct TaskPool {
     double ray[S][6];  // published ray (origin, direction)
     float col[S][4];   // the subtree's colour once done
     int depth[S];      // recursion depth of the published ray
-    uint32_t pix[S];   // owner's pixel (error reports)
+    uint32_t pix[S];   // owner's pixel (error reports; the area family's light positions)
     int done[S];       // 1: col holds the result
     uint32_t free_m[S / 32];  // 1 = slot free
     uint32_t pend_m[S / 32];  // 1 = published, not taken

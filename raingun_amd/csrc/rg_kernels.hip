@@ -181,6 +181,8 @@ static hipError_t launch_depth(const RgKernelArgs *a, hipStream_t stream, size_t
 // plain (nullable): whether the launch runs a PLAIN light instantiation (rg_render_launch.h rg_light_plain)
 static hipError_t dispatch_depth(const RgKernelArgs *a, int maxd, hipStream_t stream, size_t *gt, int *plain = nullptr) {
     if (plain) *plain = 0;
+    if (a->area_tab)  // a band of a supersampled frame with area lights (rg_render_*_area.hip): the lens family's launch, lights per sample
+        return rg_heavy_path(*a) ? launch_heavy<RG_MAXD_AREA, false>(a, stream, gt) : launch_light<RG_MAXD_AREA>(a, stream, gt, plain);
     if (a->lens)  // a band of a supersampled frame through a thin lens (rg_render_*_lens.hip): the camera family's launch, lens rays
         return rg_heavy_path(*a) ? launch_heavy<RG_MAXD_LENS, false>(a, stream, gt) : launch_light<RG_MAXD_LENS>(a, stream, gt, plain);
     if (a->camera) {  // a camera launch (rg_render_*_camera*.hip): primary rays from the eye, frames in the global buffer

@@ -20,6 +20,7 @@
 #include "rg_exact.h"
 #include "rg_internal.h"
 #include "rg_launchers.h"
+#include "rg_area.h"
 #include "rg_lens.h"
 
 #pragma clang fp contract(off)
@@ -49,6 +50,7 @@ rg_status validate(const rg_scene *s, const rg_launch_desc &d, uint32_t *out_row
     if (d.lens_k && (d.px_mask || d.host_frame || d.tile_wlog != 3 || d.lens_k > RG_LENS_MAX_SAMPLES ||
                      d.width % d.lens_k != 0 || (rg_lens_active(s->lens.aperture, d.lens_k) && !d.lens_tab)))
         return RG_ERR_INVALID_ARGUMENT;
+    if (rg_area_active(s->area_any, d.lens_k) && (!d.area_tab || !d.lens_tab)) return RG_ERR_INVALID_ARGUMENT;
     if (rg_lens_active(s->lens.aperture, d.lens_k) && s->has_camera) {
         // the lens disk's axes are the camera's right and up, normalized: a zero (or overflowing) one spans no disk
         double lr[3], lu[3];
@@ -120,6 +122,17 @@ RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx
         rg_lens_axis(a.cam_right, s->lens.aperture, a.lens_r);
         rg_lens_axis(a.cam_up, s->lens.aperture, a.lens_u);
         a.lens_tab = d.lens_tab;
+    }
+    if (rg_area_active(s->area_any, d.lens_k)) {  // by reference: the scene's device table (rg_scene_set_light_radii)
+        if (!a.camera) {  // the reference's view as a camera: the area family is the camera family's
+            a.camera = 1u;
+            a.cam_right[0] = a.cam_up[1] = 1.0;
+            a.cam_forward[2] = -1.0;
+            a.plain_veto |= 4u;
+        }
+        a.lens_k = d.lens_k;
+        a.lens_tab = d.lens_tab;  // the turns
+        a.area_tab = d.area_tab;
     }
     a.rgba = reinterpret_cast<uint32_t *>(d.rgba);
     a.rgb = d.rgb;
@@ -372,6 +385,15 @@ rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_
     if (!rg_heavy_path(a)) {  // light path: one staging loop per block
         a.lds_blob = rg_lds_blob_for(s, a);
         if (!a.lds_blob) a.plain_veto |= 2u;  // the PLAIN kernels' two tables exist in the image only
+    }
+    if (a.area_tab) {
+        // No light buffers: a light's grid is exact for rays towards the light's own position only, and each
+        // sample sees the light elsewhere, so shadow rays walk the BVH; the camera buffer goes with them.
+        // (After the arena's image is made: its layout and content are the scene's, whatever this launch reads.)
+        a.lbuf = nullptr;
+        a.lb_start = a.lb_ent = nullptr;
+        a.n_lbuf = 0;
+        a.lb_cam = -1;
     }
     if (d.timed && !ok(hipEventRecord(cx->ev0, d.stream))) return RG_ERR_DEVICE;  // kernel_ms includes the tile probe
     // a sparse launch's list only schedules: no probe, and the cached order and its key stay as they are

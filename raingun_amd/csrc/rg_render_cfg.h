@@ -54,6 +54,10 @@ constexpr int RG_MAXD_CAMERA = -1;
 // ... and RG_MAXD_LENS: the lens family -- the camera family's kernels whose primary rays leave a point of
 // the launch's lens disk for the plane in focus (rg_lens.h; the bands of a supersampled frame, rg_aa.hip).
 constexpr int RG_MAXD_LENS = -2;
+// ... and RG_MAXD_AREA: the area family -- the lens family's kernels (the lens ray where the launch has a
+// lens, the camera ray otherwise: uniform across the launch) whose spherical lights are seen at a point of
+// their sphere per sample (rg_area.h; the bands of a supersampled frame of a scene with light radii).
+constexpr int RG_MAXD_AREA = -3;
 constexpr bool rg_lbt_light(int lbt) { return lbt != RG_LBT_HEAVY; }
 constexpr int rg_lbt_of_lights(int lights) { return lights == 1 ? -1 : lights; }
 // The kernel's launch bounds (its attribute stands in front of any `using K`).  Light path: blocks of
@@ -64,7 +68,7 @@ constexpr int rg_min_waves_per_eu(int lbt, int wps) { return rg_lbt_light(lbt) ?
 
 // MAXD: array frames per lane (0: frames in the global buffer; RG_MAXD_CAMERA: the same, and the
 // primary rays of a movable camera, rg_camera.h -- the camera family; RG_MAXD_LENS: those through a thin
-// lens, rg_lens.h -- the lens family).  LSPH / LCOLD: which tables a block
+// lens, rg_lens.h -- the lens family; RG_MAXD_AREA: those with area lights, rg_area.h -- the area family).  LSPH / LCOLD: which tables a block
 // stages into LDS (rg_render_kernel.h).  WPS: waves per SIMD.  F32F: the f32 sphere pre-filter.  BVH:
 // the sphere BVH.  TASKS: task splitting.  HF: the host-frame features with MAXD array frames.
 // SPARSE: a tile list under a pixel mask.  PLAIN: scene facts compiled in.
@@ -78,8 +82,9 @@ struct RenderCfg {
 
     static constexpr bool light = rg_lbt_light(LBT);              // the light path (shadow batches), else the heavy path
     static constexpr int lights_per_batch = LBT < 0 ? -LBT : LBT;  // 1 on the heavy path
+    static constexpr bool area = MAXD == RG_MAXD_AREA;            // lights with a radius (rg_area.h); a lens if the launch has one
     static constexpr bool lens = MAXD == RG_MAXD_LENS;            // ... through the launch's thin lens (rg_lens.h)
-    static constexpr bool camera = MAXD == RG_MAXD_CAMERA || lens;  // primary rays from the launch's camera (rg_camera.h)
+    static constexpr bool camera = MAXD == RG_MAXD_CAMERA || lens || area;  // primary rays from the launch's camera (rg_camera.h)
     static constexpr bool global_frames = MAXD == 0 || camera;    // frames in the global buffer, no per-lane array
     static constexpr int array_frames = global_frames ? 0 : MAXD;  // the lane's frame array (rg_k_frames.h FrameStack)
     // Host-frame features (deferred tile stores, tile publication, streaming cancellation, tile
@@ -110,8 +115,9 @@ struct RenderCfg {
     static constexpr uint32_t tile_px_budget_bytes = host_frames ? (uint32_t)tile_px_rows * 64u * 4u : 0u;
 
     static_assert(!BVH || 4 * WPS <= RG_BVH_MAX_WAVES, "one BVH stack per wave");
-    static_assert(MAXD >= RG_MAXD_LENS, "MAXD: array frames, 0, RG_MAXD_CAMERA or RG_MAXD_LENS");
+    static_assert(MAXD >= RG_MAXD_AREA, "MAXD: array frames, 0, RG_MAXD_CAMERA, RG_MAXD_LENS or RG_MAXD_AREA");
     static_assert(!lens || (!SPARSE && !HF), "the lens family: dense device-resident bands only");
+    static_assert(!area || (!SPARSE && !HF), "the area family: dense device-resident bands only");
     static_assert(!SPARSE || (global_frames && !HF), "sparse launches run the global-frame kernels");
     static_assert(!PLAIN || (light && LSPH && LCOLD && !global_frames && !HF && !SPARSE),
                   "PLAIN: device-resident launches of the LDS-blob light kernels");

@@ -36,6 +36,7 @@
 #include "rg_k_pool.h"
 #include "rg_k_shade.h"
 #include "rg_k_trace.h"
+#include "rg_area.h"
 #include "rg_lens.h"
 #include "rg_render_cfg.h"
 #include "rg_shadow_vol_cell.h"
@@ -76,6 +77,31 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
     for (uint32_t k = threadIdx.x; k < bytes / 16u; k += blockDim.x) d[k] = g[k];
 }
 
+// Light l as the ray tree of sample-frame pixel `pix` sees it -- the ONE place the kernel reads a light, so that
+// direction, distance and intensity at every site agree.  The area family (K::area): a spherical light at this
+// sample's point of its sphere (rg_area.h; pix = Y * a.width + X with Y the row of the whole sample frame, for a
+// fan helper or a pool task the OWNER's pixel), by value; every other kernel: a reference to the table's entry,
+// as if it read it in place -- its code is the code it had.
+template <class K>
+__device__ __forceinline__ decltype(auto) light_at(const RgKernelArgs &a, const RgLightDev *lights, int l,
+                                                   [[maybe_unused]] uint32_t pix) {
+    if constexpr (K::area) {
+        RgLightDev L = lights[l];
+        if (L.kind != RG_LIGHT_DIRECTIONAL) {
+            double pos[3];
+            rg_area_position(L.v, a.area_tab[RG_AREA_POINT_DOUBLES + (uint32_t)l], pix % a.width, pix / a.width, a.lens_k,
+                             a.width / a.lens_k, (uint32_t)l, a.area_tab + 3u * rg_lens_points_offset(a.lens_k),
+                             a.lens_tab + 2u * RG_LENS_POINTS, pos);
+            L.v[0] = pos[0];
+            L.v[1] = pos[1];
+            L.v[2] = pos[2];
+        }
+        return L;
+    } else {
+        return (lights[l]);
+    }
+}
+
 // Render kernel.  Heavy path: ONE persistent block of 256*WPS threads per CU
 // (WPS waves per SIMD).  Light path: one-wave blocks, each rendering at most
 // RG_LIGHT_TILES_PER_WAVE tiles (grid: rg_render_grid.h).  A block stages the
@@ -94,6 +120,9 @@ __device__ __forceinline__ void stage16(unsigned char *dst, const void *src, uin
 // a.cam_eye in the directions of rg_camera.h and are traced by the general closest-hit query.
 // MAXD == RG_MAXD_LENS (the lens family): that kernel again, whose primary rays are the lens
 // rays of rg_lens.h -- the one difference, at the RGR_PRIM site.
+// MAXD == RG_MAXD_AREA (the area family): the lens family's kernel (the lens ray where a.lens, the
+// camera ray otherwise) whose every light is read through light_at: a spherical light stands at the point of
+// its sphere that rg_area.h gives the sample whose ray tree the lane is tracing.
 // SPARSE (global frames only): the queue hands out the launch's tile LIST a.tile_perm[0 .. a.tile_limit) and a lane
 // renders its pixel only where a.px_mask says so (adaptive anti-aliasing, rg_aa.hip; RgKernelArgs::px_mask).
 template <int MAXD, bool LSPH, bool LCOLD, int WPS, int LBT, bool F32F, bool BVH, bool TASKS, int TPW = 0,
@@ -409,7 +438,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #pragma unroll
                             for (int l = 0; l < LB; ++l) {
                                 if (l < n_lights) {
-                                    const RgLightDev L = T.lights[l];
+                                    const RgLightDev L = light_at<K>(a, T.lights, l, pixel);
                                     if (L.kind != RG_LIGHT_DIRECTIONAL) RG_REGION(RGR_LIGHT_SPH);
                                     light_dir_dist<UL>(L, h, sb.d[l], sb.ld[l]);
                                     park[64 * (PK_PP + l)] = fmaxf((float)dot(n, sb.d[l]), 0.0f);  // rendering.rs:161-162
@@ -518,7 +547,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #pragma unroll
                 for (int l = 0; l < LB; ++l) {
                     if (l < n_lights) {
-                        const RgLightDev L = T.lights[l];
+                        const RgLightDev L = light_at<K>(a, T.lights, l, pixel);
                         const float inten = !((occl >> l) & 1u) ? park[64 * (PK_LIN + l)] : 0.0f;
                         const float power = park[64 * (PK_PP + l)] * inten;
                         C3 lc = cscl(cscl(c3(L.color[0], L.color[1], L.color[2]), power), refl);
@@ -557,7 +586,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #pragma unroll
                     for (int l = 0; l < LB; ++l) {
                         if (li + l < a.n_lights) {
-                            const RgLightDev L = T.lights[li + l];
+                            const RgLightDev L = light_at<K>(a, T.lights, li + l, pixel);
                             float inten = !((occl >> l) & 1u) ? light_intensity(L, hp) : 0.0f;
                             float power = fmaxf((float)dot(hn, sb.d[l]), 0.0f) * inten;
                             C3 lc = cscl(cscl(c3(L.color[0], L.color[1], L.color[2]), power), refl);
@@ -567,7 +596,7 @@ void rg_render_kernel(RgKernelArgs a) {
                     if constexpr (K::shadow_fan) {
                         // the lights helper lanes traced, in light order (rendering.rs:141-170)
                         for (int k = 0; k < nfan; ++k) {
-                            const RgLightDev L = T.lights[li + 1 + k];
+                            const RgLightDev L = light_at<K>(a, T.lights, li + 1 + k, pixel);
                             V3 ldir;
                             double ldist;
                             light_dir_dist<UL>(L, hp, ldir, ldist);  // as at setup: same bits
@@ -587,7 +616,7 @@ void rg_render_kernel(RgKernelArgs a) {
 #pragma unroll
                     for (int l = 0; l < LB; ++l) {
                         if (li + l < a.n_lights) {
-                            light_dir_dist<UL>(T.lights[li + l], hp, sb.d[l], sb.ld[l]);
+                            light_dir_dist<UL>(light_at<K>(a, T.lights, li + l, pixel), hp, sb.d[l], sb.ld[l]);
                             occl_full |= 1u << l;
                             n_shadow++;
                         } else {
@@ -855,7 +884,9 @@ void rg_render_kernel(RgKernelArgs a) {
                         // traces as the general closest-hit query at depth 0 that it is -- nothing of
                         // trace_primary's o = 0 (sph_cc, the planes' o.n, the camera buffer) holds for it
                         double dir[3];
-                        if constexpr (K::lens) {
+                        // (the area family: with the launch's lens if it has one -- uniform across the launch;
+                        // a constant for every other kernel)
+                        if (K::lens || (K::area && a.lens != 0u)) {
                             // ... through the launch's thin lens (rg_lens.h): this sample's point of the lens
                             // disk, turned by the output pixel's hash, towards the plane in focus
                             double org[3];
@@ -932,7 +963,7 @@ void rg_render_kernel(RgKernelArgs a) {
                             }
 #pragma unroll
                             for (int l = 0; l < LB; ++l) {
-                                const RgLightDev L = T.lights[l];
+                                const RgLightDev L = light_at<K>(a, T.lights, l, pixel);
                                 light_dir_dist<UL>(L, h, sb.d[l], sb.ld[l]);
                                 pp[l] = fmaxf((float)dot(n, sb.d[l]), 0.0f);  // rendering.rs:161-162
                                 lin[l] = light_intensity(L, h);               // pure; used if lit
@@ -965,7 +996,7 @@ void rg_render_kernel(RgKernelArgs a) {
                                 C3 acc = c3(0.0f, 0.0f, 0.0f);
 #pragma unroll
                                 for (int l = 0; l < LB; ++l) {
-                                    const RgLightDev L = T.lights[l];
+                                    const RgLightDev L = light_at<K>(a, T.lights, l, pixel);
                                     const float inten = !((focc >> l) & 1u) ? lin[l] : 0.0f;
                                     const float power = pp[l] * inten;
                                     const C3 lc = cscl(cscl(c3(L.color[0], L.color[1], L.color[2]), power), refl);
@@ -1018,7 +1049,7 @@ void rg_render_kernel(RgKernelArgs a) {
                             q.o = oso;  // hit + n * bias (rendering.rs:148)
                             hdepth = ohd;
                             pixel = opix;  // error reports name the owner's pixel
-                            light_dir_dist<UL>(T.lights[oli + 1 + k], hp, sb.d[0], sb.ld[0]);
+                            light_dir_dist<UL>(light_at<K>(a, T.lights, oli + 1 + k, pixel), hp, sb.d[0], sb.ld[0]);
                             li = oli + 1 + k;  // the light this helper traces (its li is unused otherwise)
                             mode = MODE_SHADOW_H;
                         }

@@ -4,7 +4,7 @@
 // launch_light<MAXD, SPARSE> / launch_heavy<MAXD, HF, SPARSE> are instantiated explicitly, one per
 // rg_render_*.hip (SPARSE: the launches of a tile list under a pixel mask, global frames only;
 // MAXD = RG_MAXD_CAMERA: the launches of a scene with a camera; MAXD = RG_MAXD_LENS: the bands of a
-// supersampled frame through a thin lens), so every
+// supersampled frame through a thin lens; MAXD = RG_MAXD_AREA: those of a scene with light radii), so every
 // rg_render_kernel instantiation is emitted by exactly one translation unit (the occupancy cache
 // and the HIP runtime identify a kernel by its host address); the dispatcher (rg_kernels.hip
 // dispatch_depth) sees only the declarations below.
@@ -236,3 +236,6 @@ extern template hipError_t launch_heavy<RG_MAXD_CAMERA, false, true>(const RgKer
 // the lens family (rg_render_*_lens.hip): dense only, light and heavy
 extern template hipError_t launch_light<RG_MAXD_LENS>(const RgKernelArgs *, hipStream_t, size_t *, int *);
 extern template hipError_t launch_heavy<RG_MAXD_LENS, false>(const RgKernelArgs *, hipStream_t, size_t *);
+// the area family (rg_render_*_area.hip): dense only, light and heavy
+extern template hipError_t launch_light<RG_MAXD_AREA>(const RgKernelArgs *, hipStream_t, size_t *, int *);
+extern template hipError_t launch_heavy<RG_MAXD_AREA, false>(const RgKernelArgs *, hipStream_t, size_t *);

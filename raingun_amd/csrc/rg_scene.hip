@@ -18,6 +18,7 @@
 #include "rg_camera.h"
 #include "rg_device.h"
 #include "rg_exact.h"
+#include "rg_area.h"
 #include "rg_lens.h"
 #include "rg_lightbuf.h"
 #include "rg_shadow_vol.h"
@@ -340,6 +341,28 @@ rg_status rg_scene_replica(const rg_scene *src, int32_t device, rg_scene **out) 
 
 void rg_scene_free(rg_scene *s) { release(s); }
 
+rg_status rg_area_upload(rg_scene *s) {
+    const uint32_t n = rg_area_table_doubles((uint32_t)s->n_lights);
+    std::vector<double> table(n, 0.0);
+    rg_area_make_table_points(table.data());
+    for (size_t l = 0; l < s->light_radii.size() && l < (size_t)s->n_lights; ++l) table[RG_AREA_POINT_DOUBLES + l] = s->light_radii[l];
+    if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
+    if (!s->d_area) {
+        void *p = nullptr;
+        if (!ok(hipMalloc(&p, n * sizeof(double)))) {
+            (void)hipGetLastError();
+            return RG_ERR_OUT_OF_MEMORY;
+        }
+        s->allocations.push_back(p);
+        s->d_area = static_cast<double *>(p);
+    }
+    // launches enqueued earlier read the table by reference: let them finish, then rewrite it
+    if (!ok(hipDeviceSynchronize()) || !ok(hipMemcpy(s->d_area, table.data(), n * sizeof(double), hipMemcpyHostToDevice)))
+        return RG_ERR_DEVICE;
+    s->area_stale = false;
+    return RG_OK;
+}
+
 void rg_sync_settings(rg_scene *dst, const rg_scene *src) {
     dst->max_depth = src->max_depth;
     dst->path = src->path;
@@ -351,6 +374,11 @@ void rg_sync_settings(rg_scene *dst, const rg_scene *src) {
     dst->has_camera = src->has_camera;
     dst->camera = src->camera;
     dst->lens = src->lens;
+    if (dst->light_radii != src->light_radii) {  // the replica's device table follows when a frame needs it
+        dst->light_radii = src->light_radii;
+        dst->area_stale = true;
+    }
+    dst->area_any = src->area_any;
     dst->lane_min_depth = src->lane_min_depth;
     dst->tile_order = src->tile_order;
     dst->ring_flush_small = src->ring_flush_small;
@@ -646,6 +674,40 @@ rg_status rg_scene_set_lens(rg_scene *s, const rg_lens *lens) {
     }
     if (!rg_lens_valid(lens->aperture, lens->focus)) return RG_ERR_INVALID_ARGUMENT;
     s->lens = *lens;
+    return RG_OK;
+}
+
+rg_status rg_scene_set_light_radii(rg_scene *s, const double *radii, uint32_t n) {
+    if (!s) return RG_ERR_INVALID_ARGUMENT;
+    if (!radii) {  // point lights again: the launches and kernels of a scene that never had radii
+        s->light_radii.clear();
+        s->area_any = false;
+        return RG_OK;
+    }
+    if (n != (uint32_t)s->n_lights || !s->host) return RG_ERR_INVALID_ARGUMENT;
+    bool any = false;
+    for (uint32_t l = 0; l < n; ++l) {
+        if (!rg_area_radius_valid(radii[l])) return RG_ERR_INVALID_ARGUMENT;
+        // a directional light has no position to spread
+        if (radii[l] > 0.0 && s->host->lights[l].kind == RG_LIGHT_DIRECTIONAL) return RG_ERR_INVALID_ARGUMENT;
+        any |= radii[l] > 0.0;
+    }
+    const std::vector<double> kept = s->light_radii;
+    s->light_radii.assign(radii, radii + n);
+    if (any) {  // only frames with a radius > 0 read the table
+        const rg_status st = rg_area_upload(s);
+        if (st != RG_OK) {
+            s->light_radii = kept;
+            return st;
+        }
+    }
+    s->area_any = any;
+    return RG_OK;
+}
+
+rg_status rg_area_tables(uint32_t samples, double *points) {
+    if (samples < 1 || samples > RG_LENS_MAX_SAMPLES || !points) return RG_ERR_INVALID_ARGUMENT;
+    rg_area_make_points(samples, points);
     return RG_OK;
 }
 

@@ -3,8 +3,8 @@
 // the HIP renderer (libraingun_hip.so: rg_render_image).
 //
 //   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
-//           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D] [--aov LAYERS] [-o FILE]
-//           [--gpu N] FILE
+//           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D] [--light-radius R[,R...]]
+//           [--aov LAYERS] [-o FILE] [--gpu N] FILE
 //
 // --aov LAYERS (not in the reference): a comma list of body, depth, normal, uv, albedo, or `all`.  Next to
 // `-o out.png` the run also writes `out.<layer>.png` for each named layer: what lies under each pixel
@@ -18,6 +18,10 @@
 // forward lengths away (rg_scene_set_lens): depth of field from the N x N rays of --samples.  They go
 // together, need --samples 2 or more and refuse --adaptive (argument errors otherwise), and combine with
 // the camera and the size flags.
+// --light-radius R (not in the reference): every spherical light of the scene gets the radius R in world units
+// (rg_scene_set_light_radii): soft shadows from the N x N rays of --samples.  A comma list gives one radius per
+// light in YAML order (0 for a directional light).  It needs --samples 2 or more and refuses --adaptive
+// (argument errors otherwise), and combines with the camera and the lens.
 // --adaptive T (0..256; not in the reference): the N x N rays only for pixels whose 8-neighbourhood
 // contrast in the 1-sample frame is at least T (rg_render_image_aa_adaptive); accepted with
 // --samples 1, where it has no effect.
@@ -63,6 +67,7 @@ const char *kHelp =
     "        --up <X,Y,Z>           Up hint of --look-at (default 0,1,0).\n"
     "        --aperture <R>         Lens radius in world units (with --focus and --samples 2 or more).\n"
     "        --focus <D>            Distance of the plane in focus, in lengths of the forward vector.\n"
+    "        --light-radius <R>     Radius of every spherical light in world units, or R,R,.. one per light (with --samples 2 or more).\n"
     "        --aov <LAYERS>         Also write FILENAME.<layer>.png for each of body,depth,normal,uv,albedo (or all).\n"
     "        --adaptive <T>         Adaptive anti-aliasing: the N x N rays only where the 1-sample frame's contrast is at least T (0..256).\n"
     "        --gpu <N>              HIP device to render on (default 0).\n"
@@ -87,7 +92,8 @@ const char *kHelp =
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
     const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr,
-               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr, *aperture = nullptr, *focus = nullptr;
+               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr, *aperture = nullptr, *focus = nullptr,
+               *light_radius = nullptr;
     int gpu = 0;
 };
 
@@ -102,6 +108,7 @@ struct RenderOptions {  // render.rs:32-46
     rg_camera camera{};
     bool has_lens = false;  // --aperture / --focus
     rg_lens lens{0.0, 1.0};
+    std::vector<double> light_radii;  // --light-radius as given: one number, or one per light (empty: no flag)
     bool aov[5] = {false, false, false, false, false};  // --aov: body, depth, normal, uv, albedo
     bool any_aov = false;
 };
@@ -176,6 +183,7 @@ Args parse_args(int argc, char **argv) {
             else if (name == "aov") a.aov = take_value(i, "--aov <LAYERS>", val);
             else if (name == "aperture") a.aperture = take_value(i, "--aperture <R>", val);
             else if (name == "focus") a.focus = take_value(i, "--focus <D>", val);
+            else if (name == "light-radius") a.light_radius = take_value(i, "--light-radius <R>", val);
             else if (val) clap_error("Found argument '" + std::string(arg) + "' which wasn't expected, or isn't valid in this context");
             else if (name == "4k") { a.uhd = true; a.hd = false; }   // overrides_with("hd")
             else if (name == "hd") { a.hd = true; a.uhd = false; }   // overrides_with("4k")
@@ -251,6 +259,21 @@ RenderOptions options_from(const Args &a) {  // main.rs:70-96
         if (o.samples < 2) clap_error("The argument '--aperture <R>' needs '--samples <N>' of 2 or more");
         if (o.has_adaptive) clap_error("The argument '--aperture <R>' cannot be used with '--adaptive <T>'");
         o.has_lens = true;
+    }
+    if (a.light_radius) {
+        const std::string spec = a.light_radius;
+        for (size_t pos = 0;;) {
+            const size_t comma = spec.find(',', pos);
+            const std::string item = spec.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+            double r = 0.0;
+            if (!parse_f64(item.c_str(), &r) || r < 0.0)
+                clap_error(std::string("Invalid value for '--light-radius <R>': ") + a.light_radius);
+            o.light_radii.push_back(r);
+            if (comma == std::string::npos) break;
+            pos = comma + 1;
+        }
+        if (o.samples < 2) clap_error("The argument '--light-radius <R>' needs '--samples <N>' of 2 or more");
+        if (o.has_adaptive) clap_error("The argument '--light-radius <R>' cannot be used with '--adaptive <T>'");
     }
     if (a.draft) {
         o.has_depth = true;
@@ -380,6 +403,21 @@ int main(int argc, char **argv) {
         panic(std::string("rg_scene_set_camera: ") + rg_status_string(st));
     if (opts.has_lens && (st = rg_scene_set_lens(scene, &opts.lens)) != RG_OK)
         panic(std::string("rg_scene_set_lens: ") + rg_status_string(st));
+    if (!opts.light_radii.empty()) {
+        // one number: every spherical light (a directional one stays hard); a list: one per light in YAML order
+        const rg_scene_desc *desc = rgh_scene_desc(loaded);
+        std::vector<double> radii(opts.light_radii);
+        if (radii.size() == 1) {
+            radii.assign(desc->n_lights, 0.0);
+            for (uint32_t l = 0; l < desc->n_lights; ++l)
+                if (desc->lights[l].kind == RG_LIGHT_SPHERICAL) radii[l] = opts.light_radii[0];
+        } else if (radii.size() != desc->n_lights) {
+            clap_error("The argument '--light-radius <R>' lists " + std::to_string(radii.size()) + " radii, the scene has " +
+                       std::to_string(desc->n_lights) + " lights");
+        }
+        if ((st = rg_scene_set_light_radii(scene, radii.data(), (uint32_t)radii.size())) != RG_OK)
+            panic(std::string("rg_scene_set_light_radii: ") + rg_status_string(st));
+    }
     std::vector<uint8_t> rgba((size_t)opts.width * opts.height * 4);
 
     auto t0 = std::chrono::steady_clock::now();  // render.rs:54-56

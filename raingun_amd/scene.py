@@ -252,6 +252,8 @@ class DeviceScene:
             self.set_bvh(bvh)
         if getattr(scene, "lens", None) is not None:  # Scene.set_lens
             self.set_lens(scene.lens)
+        if getattr(scene, "light_radii", None) is not None:  # Scene.set_light_radii
+            self.set_light_radii(scene.light_radii)
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -411,6 +413,19 @@ class DeviceScene:
             return
         l = _abi.rg_lens(float(lens.aperture), float(lens.focus))
         _abi.check(_abi.lib().rg_scene_set_lens(self.handle, C.byref(l)), "rg_scene_set_lens")
+
+    def set_light_radii(self, radii: Optional[Sequence[float]]) -> None:
+        """rg_scene_set_light_radii: one radius (world units) per light, in the scene's order, for every later
+        render_image_aa / render_aa_async with samples >= 2 -- soft shadows; a directional light's must be 0.
+        None, or every radius 0: point lights again.  One-ray-per-pixel renders ignore them, the adaptive
+        ones are refused while one is > 0.  Blocking: the call waits for the device to go idle before it
+        rewrites the scene's table, and launches enqueued later see the new radii."""
+        if radii is None:
+            _abi.check(_abi.lib().rg_scene_set_light_radii(self.handle, None, 0), "rg_scene_set_light_radii")
+            return
+        r = [float(x) for x in radii]
+        _abi.check(_abi.lib().rg_scene_set_light_radii(self.handle, (C.c_double * max(len(r), 1))(*r), len(r)),
+                   "rg_scene_set_light_radii")
 
     def render_image(self, width: int, height: int, stats: Optional[_abi.rg_stats] = None,
                      out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -599,6 +614,13 @@ class Scene:                   # scene.rs:11-31
         """The thin lens (raingun_amd/camera.py Lens) that every DeviceScene made of this scene from now on
         starts with, and so render_image(samples >= 2); None: the pinhole."""
         self.lens = lens
+
+    light_radii = None  # set_light_radii: not a field of the scene file either
+
+    def set_light_radii(self, radii: Optional[Sequence[float]]) -> None:
+        """The lights' radii (DeviceScene.set_light_radii: one per light, in order) that every DeviceScene made
+        of this scene from now on starts with, and so render_image(samples >= 2); None: point lights."""
+        self.light_radii = None if radii is None else tuple(float(r) for r in radii)
 
     def to_device(self, device: int = 0) -> DeviceScene:
         return DeviceScene(self, device)

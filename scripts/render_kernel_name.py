@@ -4,11 +4,12 @@ compiler remarks, assembly and profiles: scripts/resources.py, scripts/isa_budge
 
     parse(name)    -> {"MAXD": 8, "LSPH": True, ...}, or None if name is no rg_render_kernel
     mangle(**p)    -> the name
-    describe(p)    -> "light", "heavy host", "light tpw=-1 plain", "heavy camera sparse", "light lens", ...
+    describe(p)    -> "light", "heavy host", "light tpw=-1 plain", "heavy camera sparse", "light lens", "heavy area", ...
 
 MAXD: array frames per lane; 0: frames in the global buffer; MAXD_CAMERA (-1, mangled Lin1E): the same
 with the primary rays of a movable camera (the camera family); MAXD_LENS (-2, mangled Lin2E): those
-through a thin lens (the lens family).
+through a thin lens (the lens family); MAXD_AREA (-3, mangled Lin3E): the lens family's kernels with area
+lights (the area family).
 """
 import re
 
@@ -17,6 +18,7 @@ PARAMS = [("MAXD", True), ("LSPH", False), ("LCOLD", False), ("WPS", True), ("LB
           ("BVH", False), ("TASKS", False), ("TPW", True), ("HF", False), ("SPARSE", False), ("PLAIN", False)]
 MAXD_CAMERA = -1
 MAXD_LENS = -2
+MAXD_AREA = -3
 _ARG = {True: r"Li(n?\d+)E", False: r"Lb([01])E"}
 _NAME = re.compile("^_Z16rg_render_kernelI" + "".join(_ARG[i] for _, i in PARAMS) + "Ev12RgKernelArgs$")
 
@@ -45,6 +47,8 @@ def describe(p):
         kind += " camera"
     if p["MAXD"] == MAXD_LENS:
         kind += " lens"
+    if p["MAXD"] == MAXD_AREA:
+        kind += " area"
     if p["SPARSE"]:
         kind += " sparse"
     if p["PLAIN"]:

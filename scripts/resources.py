@@ -1,6 +1,6 @@
 """Per-instantiation register/scratch summary of rg_render_kernel.
 
-    python scripts/resources.py [--camera | --lens | --aov] [extra hipcc flags...]
+    python scripts/resources.py [--camera | --lens | --area | --aov] [extra hipcc flags...]
 
 Compiles the three depth-8 files (rg_render_heavy_d8_host.hip, rg_render_light_d8.hip,
 rg_render_heavy_d8.hip) with the library's flags and -Rpass-analysis=kernel-resource-usage and prints VGPRs, spilled VGPRs, scratch bytes per lane, occupancy and static LDS for the
@@ -10,6 +10,8 @@ host-frame ones, "tpw=-1": the light path's persistent single launches).
 the MAXD = 0 kernels it derives from (rg_render_{light,heavy}_{d0,sparse}.hip), MAXD printed first.
 --lens: instead, the lens family (MAXD = -2: rg_render_{light,heavy}_lens.hip) beside the dense camera
 kernels it derives from (rg_render_{light,heavy}_camera.hip).
+--area: instead, the area family (MAXD = -3: rg_render_{light,heavy}_area.hip) beside the lens family it
+derives from (rg_render_{light,heavy}_lens.hip).
 --aov: instead, the instantiations of rg_aov_kernel (rg_aov.hip) and the out-of-line sphere_uv they call."""
 import re
 import subprocess
@@ -30,6 +32,10 @@ if "--lens" in sys.argv[1:]:
     sys.argv.remove("--lens")
     UNITS = ["rg_render_light_camera", "rg_render_light_lens", "rg_render_heavy_camera", "rg_render_heavy_lens"]
     SHOW = (-1, -2)
+if "--area" in sys.argv[1:]:
+    sys.argv.remove("--area")
+    UNITS = ["rg_render_light_lens", "rg_render_light_area", "rg_render_heavy_lens", "rg_render_heavy_area"]
+    SHOW = (-2, -3)
 AOV = "--aov" in sys.argv[1:]
 if AOV:
     sys.argv.remove("--aov")
