@@ -494,6 +494,65 @@ rg_status rg_scene_set_light_radii(rg_scene *scene, const double *radii, uint32_
  * RG_ERR_INVALID_ARGUMENT for samples outside 1 .. 8 or a null `points`. */
 rg_status rg_area_tables(uint32_t samples, double *points);
 
+/* Ambient occlusion: per pixel, the share of the hemisphere above the primary hit that is open.  The companion
+ * of the AOV layers: samples x samples any-hit rays per hit pixel, no lights, no shading.  Deterministic, no
+ * random numbers; everything f64, unfused, in the order written.  For pixel (x, y) of the frame:
+ *   1. the primary ray (o, d) is the ray rg_render_aov traces for that pixel (create_prime, or the ray of
+ *      rg_scene_set_camera), closest hit by Scene::trace (scene.rs:34-39).  On a miss ao = 1.0f and no further
+ *      ray is traced.  RG_ERR_NAN_DISTANCE where rg_render_aov raises it.
+ *   2. h = o + d * t;  n = surface_normal(body, h) -- without an AABB face (1,0,0) and RG_ERR_AABB_NORMAL, as
+ *      get_color does.
+ *   3. m = normalize(n) (plane and disk normals are the YAML's, not unit);  nf = m if dot(m, d) <= 0, else -m:
+ *      the side the ray came from.
+ *   4. O.c = h.c + nf.c * bias
+ *   5. s = copysign(1.0, nf.z);  a = -1.0 / (s + nf.z);  b = (nf.x * nf.y) * a         (Duff et al.)
+ *      T = (1.0 + (s * nf.x) * (nf.x * a),  s * b,  (-s) * nf.x)
+ *      B = (b,  s + (nf.y * nf.y) * a,  -nf.y)
+ *   6. p = y * width + x (y the row of the whole frame);  hsh = lowbias32(p), the hash of rg_lens;
+ *      (c, g) = rotations[hsh & 63], rg_lens_tables' 64 turns;
+ *      Tr.c = c * T.c + g * B.c;  Br.c = c * B.c - g * T.c               once per pixel
+ *   7. for sample j = 0 .. k^2 - 1, in this order:  (px, py, pz) = ao_points_k[j], rg_ao_tables';
+ *      D.c = (Tr.c * px + Br.c * py) + nf.c * pz;  ray = Ray::new(O, normalize(D)).
+ *      The ray is occluded iff Scene::trace finds a hit with !(t > radius): the rule of rendering.rs:150-155 with
+ *      `radius` in place of the light's distance, the scene.rs:38 panic (RG_ERR_NAN_DISTANCE) included where two
+ *      hits are compared and one is NaN.
+ *   8. ao = (float)open / (float)(k * k), open the number of rays not occluded.
+ * Ray counts: primary == the pixels rendered, shadow == k^2 x the hit pixels (AO rays count in the shadow class),
+ * secondary == 0.  Ignored by design: the scene's lens, its light radii, its lights and max_recursion_depth.
+ * rg_render_multi and rg_frames_* have no AO mode. */
+typedef struct rg_ao {
+    uint32_t samples;   /* k: k x k rays per hit pixel, 1..8 */
+    uint32_t _pad;
+    double radius;      /* > 0, may be +inf: a ray is occluded by a hit at distance t with !(t > radius) */
+    double bias;        /* >= 0, finite: the origin's offset along the facing normal (the reference's own is 1e-13) */
+} rg_ao;
+
+/* The AO pass's points, pure host code.  points: 3 * samples^2 doubles; the point at index j * samples + i is
+ * (pu, pv, sqrt(fmax(0.0, (1.0 - pu*pu) - pv*pv))) with (pu, pv) rg_lens_tables' point of that index: the unit
+ * disk lifted onto the hemisphere, so the rays are cosine-weighted (Malley).  samples == 1 and the centre cell of
+ * an odd samples: exactly (0, 0, 1).  The device holds the points of samples = 1 .. 8 in a table made once per
+ * scene on the first AO frame and never rewritten.  RG_ERR_INVALID_ARGUMENT for samples outside 1 .. 8 or a null
+ * `points`. */
+rg_status rg_ao_tables(uint32_t samples, double *points);
+
+/* Blocking whole-frame AO render into a host buffer (pageable or pinned) of width*height floats, row-major.  The
+ * frame is delivered on the reference's panics (RG_ERR_NAN_DISTANCE, RG_ERR_AABB_NORMAL); stats->error_pixel is
+ * the lowest failing pixel.  Status codes as rg_render_aov's, plus RG_ERR_INVALID_ARGUMENT for a null `ao` or
+ * `ao_out`, samples outside 1 .. 8, radius NaN or <= 0, bias negative or not finite.  A rejected call writes
+ * nothing.  `stats` may be NULL. */
+rg_status rg_render_ao(const rg_scene *scene, uint32_t width, uint32_t height, const rg_ao *ao,
+                       float *ao_out /* host, width*height */, rg_stats *stats);
+
+/* Device-resident rg_render_ao of the tiles selected by `tiling`, with rg_render_aov_async's tiling, packing and
+ * stream contract: `ao_dev` is device memory on the scene's device (rg_tiling_rows x width floats); each stream
+ * has its own launch context, launches of one scene on distinct streams may be in flight together, the camera is
+ * read at enqueue and travels by value as `ao` does, and the call is asynchronous unless `stats` is non-NULL (then
+ * it synchronises `stream`; without it rg_stream_status reports device errors).  Padding rows of a partial last
+ * tile hold 0.0f.  Also RG_ERR_INVALID_ARGUMENT for a null or bad tiling. */
+rg_status rg_render_ao_async(const rg_scene *scene, uint32_t width, uint32_t height, const rg_tiling *tiling,
+                             const rg_ao *ao, float *ao_dev /* device, rg_tiling_rows x width */, void *stream,
+                             rg_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,10 @@ class rg_aov(C.Structure):  # device or host pointers, each nullable (include/ra
                 ("albedo", C.c_void_p)]
 
 
+class rg_ao(C.Structure):  # the ambient occlusion pass, by value (include/raingun.h)
+    _fields_ = [("samples", C.c_uint32), ("_pad", C.c_uint32), ("radius", C.c_double), ("bias", C.c_double)]
+
+
 class rg_lens(C.Structure):
     _fields_ = [("aperture", C.c_double), ("focus", C.c_double)]
 
@@ -170,6 +174,9 @@ EXPORTED_SYMBOLS = (
     "rg_lens_tables",
     "rg_scene_set_light_radii",
     "rg_area_tables",
+    "rg_ao_tables",
+    "rg_render_ao",
+    "rg_render_ao_async",
 )
 # include/raingun_debug.h
 DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "rg_debug_counters",
@@ -359,6 +366,14 @@ def _declare(lib: C.CDLL) -> None:
         lib.rg_render_aov_async.restype = C.c_int32
         lib.rg_render_aov_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_tiling), P(rg_aov), C.c_void_p,
                                             P(rg_stats)]
+    if hasattr(lib, "rg_render_ao"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
+        lib.rg_ao_tables.restype = C.c_int32
+        lib.rg_ao_tables.argtypes = [C.c_uint32, P(C.c_double)]
+        lib.rg_render_ao.restype = C.c_int32
+        lib.rg_render_ao.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_ao), C.c_void_p, P(rg_stats)]
+        lib.rg_render_ao_async.restype = C.c_int32
+        lib.rg_render_ao_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_tiling), P(rg_ao), C.c_void_p,
+                                           C.c_void_p, P(rg_stats)]
     lib.rg_frames_status.restype = C.c_int32
     lib.rg_frames_status.argtypes = [C.c_void_p, P(C.c_int32)]
     if hasattr(lib, "rg_frames_set_batch"):  # absent from pre-round-3 builds

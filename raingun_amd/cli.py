@@ -2,7 +2,7 @@
 
     python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
                               [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D]
-                              [--light-radius R[,R...]] [--aov LAYERS] [-o FILE] FILE
+                              [--light-radius R[,R...]] [--aov LAYERS] [--ao K[,RADIUS[,BIAS]]] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
@@ -34,7 +34,14 @@ albedo, or `all`) also writes, next to `-o out.png`, `out.<layer>.png` for each
 named layer: what lies under each pixel (rg_render_aov), as the pictures of
 raingun_amd/aov.py visualize.  It honours the size flags and the camera;
 --samples and --adaptive affect only the beauty frame, the layers stay one ray
-per pixel.  Without --aov nothing changes, the timing line included.  The
+per pixel.  Without --aov nothing changes, the timing line included.
+`--ao K[,RADIUS[,BIAS]]` (not in the reference; K 1..8, RADIUS > 0 or inf, the
+default, BIAS >= 0, default 1e-13) also writes `out.ao.png`: the ambient
+occlusion of the frame (rg_render_ao), K x K rays over the hemisphere above
+each pixel's primary hit, as the grey picture of raingun_amd/ao.py visualize.
+It honours the size flags and the camera and is independent of --samples,
+--aperture and --light-radius; it runs after the beauty frame and outside its
+timing line.  Without --ao nothing changes.  The
 render itself runs on the GPU (rg_render_image); the scene is loaded and the
 PNG written by the native host layer (libraingun_host.so), and the timing line matches
 print_render_message (render.rs:218-244).  `--preview` (piston window) is not
@@ -51,7 +58,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import aov
+from . import ao, aov
 from .camera import (Camera, Lens, camera_from_flags, lens_from_flags, light_radii_from_flags, parse_triple,
                      spread_light_radii)
 
@@ -67,6 +74,7 @@ class RenderOptions:          # render.rs:32-46
     lens: Optional[Lens] = None      # --aperture / --focus (not in the reference)
     light_radii: Optional[tuple] = None  # --light-radius as given: one number or one per light (not in the reference)
     aov: tuple = ()           # layers of --aov, in aov.LAYERS order (not in the reference)
+    ao: Optional[tuple] = None  # --ao as (samples, radius, bias) (not in the reference)
 
 
 class _LastWins(argparse.Action):
@@ -109,6 +117,9 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("--aov", metavar="LAYERS",
                    help="Also write FILENAME.<layer>.png for each of a comma list of body, depth, normal, uv, "
                         "albedo (or all).")
+    p.add_argument("--ao", metavar="K[,RADIUS[,BIAS]]",
+                   help="Also write FILENAME.ao.png: ambient occlusion from K x K rays per pixel (K 1..8) that "
+                        "hits within RADIUS occlude (default inf), leaving BIAS above the surface (default 1e-13).")
     p.add_argument("input", metavar="FILE", help="The scene definition file, in YAML format.")
     return p
 
@@ -137,6 +148,11 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
             o.aov = aov.parse_layers(ns.aov)
         except ValueError:
             raise SystemExit("Could not parse aov") from None
+    if ns.ao is not None:
+        try:
+            o.ao = ao.parse_spec(ns.ao)
+        except ValueError:
+            raise SystemExit("Could not parse ao") from None
     if ns.draft:
         o.max_recursion_depth = 4
     elif ns.hd:
@@ -263,6 +279,9 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
         layers = ds.render_aov(opts.width, opts.height, opts.aov)
         for name in opts.aov:
             output_path.with_suffix(f".{name}.png").write_bytes(encode_png(aov.visualize(name, layers[name])))
+    if opts.ao is not None:  # out.png -> out.ao.png, whatever --samples, --aperture and --light-radius say
+        occlusion = ds.render_ao(opts.width, opts.height, *opts.ao)
+        output_path.with_suffix(".ao.png").write_bytes(encode_png(ao.visualize(occlusion)))
     ds.close()
     print(f"{input_path}\t→\t{output_path}\t({format_duration(int((t1 - t0) * 1000))} render, "
           f"{format_duration(int((t2 - t1) * 1000))} write)")

@@ -1,7 +1,7 @@
 // rg_internal.h — host-side state behind the opaque rg_scene handle, shared
 // by rg_scene.hip (scene upload, kernel arguments), rg_launch.hip (per-stream
 // launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
-// streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_frames.hip
+// streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_ao.hip (the ambient occlusion pass), rg_frames.hip
 // (frames in flight over N processes), rg_multi.hip (one process driving N
 // devices), rg_gather.hip (the pack and re-interleave kernels of both) and rg_rccl.hip
 // (the run-time RCCL loader, rg_rccl.h, and the rg_comm_* functions).  The band resource
@@ -217,6 +217,9 @@ struct rg_scene {
     std::vector<double> light_radii;
     bool area_any = false, area_stale = false;
     double *d_area = nullptr;
+    // the ambient occlusion pass's table on the device (rg_ao.h RG_AO_TABLE_DOUBLES doubles: every k's points,
+    // then the lens's rotations): made on the first AO frame (rg_ao.hip), never rewritten
+    mutable double *d_ao = nullptr;
     float bvh_obound = 0.0f;
     double bvh_rbound = 0.0, bvh_margin = 0.0, bvh_extent = 0.0;
     rg_bvh_info bvh_info{};

@@ -1,5 +1,5 @@
-// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip, rg_tile_order_camera.hip, rg_resolve.hip, rg_edge.hip
-// and rg_aov.hip define for the host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  The defining files
+// rg_launchers.h — the launchers rg_kernels.hip, rg_tile_order.hip, rg_tile_order_camera.hip, rg_resolve.hip, rg_edge.hip,
+// rg_aov.hip and rg_ao.hip define for the host side (rg_launch.hip, rg_capi.hip, rg_aa.hip).  The defining files
 // include this header too, so the compiler checks every signature against it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +32,17 @@ struct RgAovOut {
     float *normal, *uv, *albedo;
 };
 extern "C" hipError_t rg_launch_aov(const RgKernelArgs *a, const RgAovOut *o, hipStream_t stream);
+// rg_ao.hip: the ambient occlusion of the launch's pixels (rg_ao of include/raingun.h by value; rg_ao.h).  out:
+// a->out_rows x a->width floats (device), packed as a->rgba's rows; tab: the scene's device table
+// (RG_AO_TABLE_DOUBLES doubles).  Reads of `a` what rg_launch_aov reads; primary rays count into
+// a->counters[0], AO rays into a->counters[1].
+struct RgAoArgs {
+    float *out;
+    const double *tab;
+    uint32_t samples, _pad;
+    double radius, bias;
+};
+extern "C" hipError_t rg_launch_ao(const RgKernelArgs *a, const RgAoArgs *o, hipStream_t stream);
 // rg_kernels.hip: *bad (device, zeroed by the caller) += the pixels of the a->width x a->height frame whose
 // camera direction differs between the general and the PLAIN kernels' arithmetic (rg_debug_camera_check).
 extern "C" hipError_t rg_launch_camera_check(const RgKernelArgs *a, unsigned long long *bad, hipStream_t stream);

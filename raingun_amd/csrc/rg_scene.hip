@@ -89,6 +89,8 @@ void release(rg_scene *s) {
     rg_aa_res_release(s->aa);
     for (void *p : s->allocations) (void)hipFree(p);
     s->allocations.clear();
+    if (s->d_ao) (void)hipFree(s->d_ao);
+    s->d_ao = nullptr;
     if (s->lds_blob) (void)hipFree(s->lds_blob);
     s->lds_blob = nullptr;
     for (rg_launch_ctx *c : s->ctxs) rg_ctx_destroy(c);

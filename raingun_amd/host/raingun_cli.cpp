@@ -4,8 +4,15 @@
 //
 //   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
 //           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D] [--light-radius R[,R...]]
-//           [--aov LAYERS] [-o FILE] [--gpu N] FILE
+//           [--aov LAYERS] [--ao K[,RADIUS[,BIAS]]] [-o FILE] [--gpu N] FILE
 //
+// --ao K[,RADIUS[,BIAS]] (not in the reference): next to `-o out.png` the run also writes `out.ao.png`, the
+// ambient occlusion of the frame (rg_render_ao): K x K rays (K 1..8) over the hemisphere above each pixel's
+// primary hit, occluded by hits within RADIUS (> 0, `inf` the default), leaving BIAS (>= 0, default 1e-13)
+// above the surface; grey, the byte the Rust `(ao * 255.0) as u8`, alpha 255 (raingun_amd/ao.py visualize).
+// It honours the size flags and the camera, is independent of --samples, --aperture and --light-radius, and
+// runs after the beauty frame, outside its timing line.  A malformed value is an argument error.  Without
+// --ao nothing changes.
 // --aov LAYERS (not in the reference): a comma list of body, depth, normal, uv, albedo, or `all`.  Next to
 // `-o out.png` the run also writes `out.<layer>.png` for each named layer: what lies under each pixel
 // (rg_render_aov), as the pictures raingun_amd/aov.py states in numpy (visualize): every cast the Rust
@@ -68,6 +75,7 @@ const char *kHelp =
     "        --aperture <R>         Lens radius in world units (with --focus and --samples 2 or more).\n"
     "        --focus <D>            Distance of the plane in focus, in lengths of the forward vector.\n"
     "        --light-radius <R>     Radius of every spherical light in world units, or R,R,.. one per light (with --samples 2 or more).\n"
+    "        --ao <K[,RADIUS[,BIAS]]>  Also write FILENAME.ao.png: ambient occlusion, K x K rays per pixel (1..8), hits within RADIUS occlude (default inf).\n"
     "        --aov <LAYERS>         Also write FILENAME.<layer>.png for each of body,depth,normal,uv,albedo (or all).\n"
     "        --adaptive <T>         Adaptive anti-aliasing: the N x N rays only where the 1-sample frame's contrast is at least T (0..256).\n"
     "        --gpu <N>              HIP device to render on (default 0).\n"
@@ -92,7 +100,7 @@ const char *kHelp =
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
     const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr,
-               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr, *aperture = nullptr, *focus = nullptr,
+               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr, *ao = nullptr, *aperture = nullptr, *focus = nullptr,
                *light_radius = nullptr;
     int gpu = 0;
 };
@@ -111,6 +119,8 @@ struct RenderOptions {  // render.rs:32-46
     std::vector<double> light_radii;  // --light-radius as given: one number, or one per light (empty: no flag)
     bool aov[5] = {false, false, false, false, false};  // --aov: body, depth, normal, uv, albedo
     bool any_aov = false;
+    bool has_ao = false;  // --ao
+    rg_ao ao{1, 0, INFINITY, 1e-13};
 };
 
 const char *const kLayers[5] = {"body", "depth", "normal", "uv", "albedo"};
@@ -180,6 +190,7 @@ Args parse_args(int argc, char **argv) {
             else if (name == "eye") a.eye = take_value(i, "--eye <X,Y,Z>", val);
             else if (name == "look-at") a.look_at = take_value(i, "--look-at <X,Y,Z>", val);
             else if (name == "up") a.up = take_value(i, "--up <X,Y,Z>", val);
+            else if (name == "ao") a.ao = take_value(i, "--ao <K[,RADIUS[,BIAS]]>", val);
             else if (name == "aov") a.aov = take_value(i, "--aov <LAYERS>", val);
             else if (name == "aperture") a.aperture = take_value(i, "--aperture <R>", val);
             else if (name == "focus") a.focus = take_value(i, "--focus <D>", val);
@@ -233,6 +244,28 @@ RenderOptions options_from(const Args &a) {  // main.rs:70-96
             pos = comma + 1;
         }
         for (int k = 0; k < 5; ++k) o.any_aov |= (o.aov[k] |= spec == "all");
+    }
+    if (a.ao) {  // K[,RADIUS[,BIAS]]: K 1..8; RADIUS > 0, inf allowed; BIAS finite, >= 0
+        const std::string spec = a.ao;
+        std::vector<std::string> parts;
+        for (size_t pos = 0;;) {
+            const size_t comma = spec.find(',', pos);
+            parts.push_back(spec.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos));
+            if (comma == std::string::npos) break;
+            pos = comma + 1;
+        }
+        auto number = [](const std::string &t, double *out) {  // one number (inf allowed), nothing else
+            if (t.empty() || t[0] == ' ' || t[0] == '\t') return false;
+            char *end = nullptr;
+            *out = std::strtod(t.c_str(), &end);
+            return end != t.c_str() && *end == '\0';
+        };
+        bool good = parts.size() >= 1 && parts.size() <= 3 && parse_u32(parts[0].c_str(), &o.ao.samples) &&
+                    o.ao.samples >= 1 && o.ao.samples <= 8;
+        if (good && parts.size() > 1) good = number(parts[1], &o.ao.radius) && o.ao.radius > 0.0;
+        if (good && parts.size() > 2) good = number(parts[2], &o.ao.bias) && o.ao.bias - o.ao.bias == 0.0 && o.ao.bias >= 0.0;
+        if (!good) clap_error(std::string("Invalid value for '--ao <K[,RADIUS[,BIAS]]>': ") + a.ao);
+        o.has_ao = true;
     }
     if (a.up && !a.look_at) clap_error("The argument '--up <X,Y,Z>' needs '--look-at <X,Y,Z>'");
     if (a.eye || a.look_at) {
@@ -448,6 +481,19 @@ int main(int argc, char **argv) {
             st = rgh_png_write(with_layer_extension(output, kLayers[k]).c_str(), rgba.data(), opts.width, opts.height);
             if (st != RGH_OK) panic(rgh_last_error());
         }
+    }
+    if (opts.has_ao) {  // after the beauty frame and outside its timing line
+        const size_t n = (size_t)opts.width * opts.height;
+        std::vector<float> occlusion(n);
+        st = rg_render_ao(scene, opts.width, opts.height, &opts.ao, occlusion.data(), nullptr);
+        if (st != RG_OK) panic(rg_status_string(st));
+        for (size_t i = 0; i < n; ++i) {  // raingun_amd/ao.py visualize
+            uint8_t *p = rgba.data() + 4 * i;
+            p[0] = p[1] = p[2] = f32_to_u8(occlusion[i] * 255.0f);
+            p[3] = 255;
+        }
+        st = rgh_png_write(with_layer_extension(output, "ao").c_str(), rgba.data(), opts.width, opts.height);
+        if (st != RGH_OK) panic(rgh_last_error());
     }
     rg_scene_destroy(scene);
     rgh_scene_free(loaded);

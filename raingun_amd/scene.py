@@ -588,6 +588,39 @@ class DeviceScene:
         _abi.check(status, "rg_render_aov_async")
         return out
 
+    def render_ao(self, width: int, height: int, samples: int, radius: float = float("inf"), bias: float = 1e-13,
+                  stats: Optional[_abi.rg_stats] = None) -> np.ndarray:
+        """rg_render_ao: the ambient occlusion of the frame render_aov renders (raingun_amd/ao.py) -- per hit pixel
+        samples x samples any-hit rays over the hemisphere above the primary hit, the open share as float32;
+        1.0 on a miss.  Returns an (H, W) float32 array.  A device error (the reference's panics) raises
+        RaingunError, as render_image does; `stats` then names the first failing pixel."""
+        out = np.empty((height, width), dtype=np.float32)
+        v = _abi.rg_ao(int(samples), 0, float(radius), float(bias))
+        st = stats if stats is not None else _abi.rg_stats()
+        _abi.check(_abi.lib().rg_render_ao(self.handle, width, height, C.byref(v), out.ctypes.data, C.byref(st)),
+                   "rg_render_ao")
+        return out
+
+    def render_ao_tiles(self, width: int, height: int, samples: int, radius: float = float("inf"), bias: float = 1e-13,
+                        tile_rows: int = 0, stride: int = 1, offset: int = 0, stream: int = 0,
+                        stats: Optional[_abi.rg_stats] = None, out=None):
+        """rg_render_ao_async: the ambient occlusion of the tiles a tiling selects (render_tiles' packing), in
+        device memory, enqueued on `stream` (a hipStream_t value).  Returns a (rows, W) float32 torch tensor on
+        this scene's device; `out` supplies the tensor to write into.  Asynchronous unless `stats` is given:
+        the caller synchronises `stream` before reading the tensor."""
+        import torch
+
+        t = _abi.rg_tiling(tile_rows or height, stride, offset)
+        rows = _abi.lib().rg_tiling_rows(height, C.byref(t))
+        if out is None:
+            out = torch.empty((rows, width), dtype=torch.float32, device=torch.device("cuda", self.device))
+        assert tuple(out.shape) == (rows, width) and out.dtype == torch.float32 and out.is_contiguous()
+        v = _abi.rg_ao(int(samples), 0, float(radius), float(bias))
+        status = _abi.lib().rg_render_ao_async(self.handle, width, height, C.byref(t), C.byref(v), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(stream), C.byref(stats) if stats is not None else None)
+        _abi.check(status, "rg_render_ao_async")
+        return out
+
     def trace(self, rays: np.ndarray):
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         n = rays.shape[0]
@@ -648,6 +681,16 @@ class Scene:                   # scene.rs:11-31
         try:
             ds.set_camera(camera)
             return ds.render_aov(width, height, layers)
+        finally:
+            ds.close()
+
+    # the ambient occlusion of render_aov's frame (rg_render_ao; raingun_amd/ao.py): an (H, W) float32 array
+    def render_ao(self, width: int, height: int, samples: int, radius: float = float("inf"), bias: float = 1e-13,
+                  device: int = 0, camera: Optional[Camera] = None) -> np.ndarray:
+        ds = DeviceScene(self, device)
+        try:
+            ds.set_camera(camera)
+            return ds.render_ao(width, height, samples, radius, bias)
         finally:
             ds.close()
 

@@ -1,6 +1,6 @@
 """Per-instantiation register/scratch summary of rg_render_kernel.
 
-    python scripts/resources.py [--camera | --lens | --area | --aov] [extra hipcc flags...]
+    python scripts/resources.py [--camera | --lens | --area | --aov | --ao] [extra hipcc flags...]
 
 Compiles the three depth-8 files (rg_render_heavy_d8_host.hip, rg_render_light_d8.hip,
 rg_render_heavy_d8.hip) with the library's flags and -Rpass-analysis=kernel-resource-usage and prints VGPRs, spilled VGPRs, scratch bytes per lane, occupancy and static LDS for the
@@ -12,7 +12,8 @@ the MAXD = 0 kernels it derives from (rg_render_{light,heavy}_{d0,sparse}.hip), 
 kernels it derives from (rg_render_{light,heavy}_camera.hip).
 --area: instead, the area family (MAXD = -3: rg_render_{light,heavy}_area.hip) beside the lens family it
 derives from (rg_render_{light,heavy}_lens.hip).
---aov: instead, the instantiations of rg_aov_kernel (rg_aov.hip) and the out-of-line sphere_uv they call."""
+--aov: instead, the instantiations of rg_aov_kernel (rg_aov.hip) and the out-of-line sphere_uv they call.
+--ao: instead, the instantiations of rg_ao_kernel (rg_ao.hip), SGPR spills (to VGPR lanes, no memory) too."""
 import re
 import subprocess
 import sys
@@ -40,6 +41,10 @@ AOV = "--aov" in sys.argv[1:]
 if AOV:
     sys.argv.remove("--aov")
     UNITS = ["rg_aov"]
+AO = "--ao" in sys.argv[1:]
+if AO:
+    sys.argv.remove("--ao")
+    UNITS = ["rg_ao"]
 procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
                            "-fno-fast-math", "-fPIC", "-c", u + ".hip", "-o", f"/tmp/{u}_res.o",
                            "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:]],
@@ -57,7 +62,7 @@ for line in remarks:
         cur = {"name": m.group(1)}
         rows.append(cur)
         continue
-    m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
+    m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None:
         cur[m.group(1)] = int(m.group(2))
 for r in rows if AOV else []:
@@ -67,7 +72,14 @@ for r in rows if AOV else []:
     what = "sphere_uv (out of line)" if m is None else "rg_aov_kernel<CAMERA %s, F32F %s, BVH %s, SHADE %s>" % m.groups()
     print(f"{what:52s}  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}"
           f"  scratch {r.get('ScratchSize [bytes/lane]')} B/lane  occ {r.get('Occupancy [waves/SIMD]')}  lds {r.get('LDS Size [bytes/block]')}")
-for r in [] if AOV else rows:
+for r in rows if AO else []:
+    m = re.match(r"_Z12rg_ao_kernelILb(\d)ELb(\d)ELb(\d)EE", r["name"])
+    if m is None:
+        continue
+    what = "rg_ao_kernel<CAMERA %s, F32F %s, BVH %s>" % m.groups()
+    print(f"{what:44s}  VGPRs {r.get('VGPRs')}  spill {r.get('VGPRs Spill')}  sgpr spill {r.get('SGPRs Spill')}"
+          f"  scratch {r.get('ScratchSize [bytes/lane]')} B/lane  occ {r.get('Occupancy [waves/SIMD]')}  lds {r.get('LDS Size [bytes/block]')}")
+for r in [] if AOV or AO else rows:
     k = parse(r["name"])
     if k is None or k["MAXD"] not in SHOW:
         continue
