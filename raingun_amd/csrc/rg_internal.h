@@ -1,5 +1,6 @@
-// rg_internal.h — host-side state behind the opaque rg_scene handle, shared
-// by rg_scene.hip (scene upload, kernel arguments), rg_launch.hip (per-stream
+// rg_internal.h — host-side state behind the opaque rg_scene handle (what the description
+// determines is in rg_scene_tables.h, built without a device by rg_scene_build.cpp), shared
+// by rg_scene.hip (scene upload, replicas, kernel arguments), rg_launch.hip (per-stream
 // launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
 // streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_ao.hip (the ambient occlusion pass), rg_frames.hip
 // (frames in flight over N processes), rg_multi.hip (one process driving N
@@ -23,6 +24,7 @@
 #include "rg_copy_pool.h"
 #include "rg_device.h"
 #include "rg_lightbuf_ray.h"
+#include "rg_scene_tables.h"
 #include "rg_tile_deal.h"
 
 inline bool ok(hipError_t e) { return e == hipSuccess; }
@@ -139,68 +141,19 @@ struct rg_aa_res : rg_band_res {
     double *d_lens = nullptr;
 };
 
-// Everything rg_scene_create uploads, as host tables (kept for replicas on
-// other devices: rg_render_multi).
-struct rg_host_tables {
-    std::vector<RgSph> sph;
-    std::vector<RgSphF> sphf;
-    std::vector<RgSphF2> sphf2;
-    std::vector<double> sph_cc;
-    std::vector<int32_t> sph_id, pln_id, dsk_id, box_id;
-    std::vector<RgPln> pln;
-    std::vector<RgDsk> dsk;
-    std::vector<RgBox> box;
-    std::vector<RgBodyDev> bodies;
-    std::vector<RgMatDev> mats;
-    std::vector<RgLightDev> lights;
-    std::vector<RgBvhNode> nodes;
-    std::vector<RgLightBufDev> lbuf;           // per light (kind RG_LB_NONE: no buffer), first RG_LB_MAX_LIGHTS lights
-    std::vector<uint32_t> lb_start, lb_ent;    // every light's cell starts / list entries, concatenated
-    std::vector<uint32_t> shvol;               // the shadow mask volume's words (rg_shadow_vol.h), empty: none
-    std::vector<uint32_t> tex_w, tex_h;
-    std::vector<std::vector<uint32_t>> texels;
-};
-
 struct rg_multi_res;  // rg_multi.hip
 struct rg_frames;     // rg_frames.hip (include/raingun_frames.h)
 
-struct rg_scene {
-    int device = 0;
-    double fov = 90.0;
-    float def[3] = {0, 0, 0};
+// What the setters change after creation and a launch reads.  A replica on another device follows
+// its root scene's, whole, before every frame (rg_sync_settings): a member added here is synced.
+struct rg_scene_settings {
     uint32_t max_depth = 10;
-    int32_t n_sph = 0, n_pln = 0, n_dsk = 0, n_box = 0, n_bodies = 0, n_lights = 0, n_textures = 0;
-    bool nan_scene = false;  // NaN distances possible (rg_k_trace.h ray_exotic)
-    std::vector<void *> allocations;
-    RgSph *sph = nullptr;
-    double *sph_cc = nullptr;
-    RgSphF *sphf = nullptr;
-    RgSphF2 *sphf2 = nullptr;
     int32_t path = RG_PATH_AUTO;
-    int32_t *sph_id = nullptr, *pln_id = nullptr, *dsk_id = nullptr, *box_id = nullptr;
-    RgPln *pln = nullptr;
-    RgDsk *dsk = nullptr;
-    RgBox *box = nullptr;
-    RgBodyDev *bodies = nullptr;
-    RgMatDev *mats = nullptr;
-    RgLightDev *lights = nullptr;
-    RgTexDev *texs = nullptr;
-    RgBvhNode *nodes = nullptr;  // sphere BVH (sphere tables are in its leaf order)
-    int32_t n_nodes = 0;
-    int32_t lane_stack = 0;      // per-lane walk stack entries the tree needs (0: per-lane walk unavailable)
     int32_t lane_min_depth = 1;  // rays of this depth and deeper walk the BVH per lane
     bool bvh_enabled = true;
-    RgLightBufDev *lbuf = nullptr;  // shadow-ray light buffers (rg_lightbuf.cpp), n_lbuf lights
-    uint32_t *lb_start = nullptr, *lb_ent = nullptr;
-    int32_t n_lbuf = 0;             // light slots (the first n_lbuf lights; kind NONE: no buffer)
-    int32_t lb_cam = -1;            // the camera buffer's index in lbuf (primary rays), -1: none
-    int32_t n_lbdesc = 0;           // descriptors in lbuf (light slots + the camera buffer)
     bool lbuf_enabled = true;       // rg_debug_set_lightbuf
-    uint32_t *shvol = nullptr;      // shadow mask volume of the PLAIN light kernels (rg_shadow_vol.cpp), null: none
     bool shvol_enabled = true;      // rg_debug_set_shadow_volume
     bool first_hit_enabled = true;  // rg_debug_set_first_hit_tiles
-    rg_shadow_volume_info shvol_info{};  // g, bytes, build time, set share; inv / off below (rg_shvol_cell's constants)
-    float shvol_inv = 0.0f, shvol_off = 0.0f;
     bool exact_div = true;          // rg_debug_set_exact_div: 0 = launches behave as if the quotient sweep had failed
     // rg_scene_set_camera: host state, read when a launch is enqueued and passed by value in its kernel
     // arguments (RgKernelArgs::camera ..), so launches in flight keep the camera they were enqueued with
@@ -209,28 +162,59 @@ struct rg_scene {
     // rg_scene_set_lens: host state like the camera, read when a band of a supersampled frame is enqueued
     // and passed by value (RgKernelArgs::lens ..); aperture == 0: no lens
     rg_lens lens{0.0, 1.0};
-    // rg_scene_set_light_radii (rg_area.h): one radius per light (empty: point lights), whether any is > 0, and
-    // the device table a band of a supersampled frame reads them from (RgKernelArgs::area_tab: every k's points,
-    // then the radii).  Unlike the camera and the lens the radii are as many as the scene has lights, so they
-    // travel by reference: the table is rewritten only with the device idle (rg_area_upload).  area_stale: the
-    // host radii are newer than the table (a replica, whose table is made when a frame first needs it).
+    // rg_scene_set_light_radii (rg_area.h): one radius per light (empty: point lights) and whether any is > 0;
+    // the device table made from them is rg_scene::d_area
     std::vector<double> light_radii;
-    bool area_any = false, area_stale = false;
-    double *d_area = nullptr;
-    // the ambient occlusion pass's table on the device (rg_ao.h RG_AO_TABLE_DOUBLES doubles: every k's points,
-    // then the lens's rotations): made on the first AO frame (rg_ao.hip), never rewritten
-    mutable double *d_ao = nullptr;
-    float bvh_obound = 0.0f;
-    double bvh_rbound = 0.0, bvh_margin = 0.0, bvh_extent = 0.0;
-    rg_bvh_info bvh_info{};
+    bool area_any = false;
     int tile_order = -1;  // expensive tiles first (rg_tile_order.hip "tile ordering"): -1 auto (heavy path), 0, 1
-    int image_bands = 0;  // host-visible frames: 0 auto, -1 one launch writing host memory, -2 split, 1..16 row bands
-    int host_split_pct = 0;  // -2 (split): percent of the frame's rows rendered into device memory + DMA (0: default)
-    mutable int split_fail_a = 0;  // debug: the next N split renders report part A's launch as failed (rg_debug_fail_split_a)
     // light-path host frames (rg_debug_set_host_ring): LDS-ring flush size and queue group of small
     // (< RG_RING_BIG_TILES tiles) and big launches
     int ring_flush_small = RG_RING_FLUSH_SMALL, ring_group_small = RG_RING_GROUP_SMALL;
     int ring_flush_big = RG_RING_FLUSH_BIG, ring_group_big = RG_RING_GROUP_BIG;
+};
+
+// A scene on one device.  Four kinds of state (DESIGN.md "Scene state"): the facts the description
+// determines (rg_scene_facts, rg_scene_tables.h) and the settings, both inherited so that their
+// members read s->n_sph, s->camera; the device tables; and the resources launches reuse.
+struct rg_scene : rg_scene_facts, rg_scene_settings {
+    int device = 0;
+    // device tables: the host tables (host, shared with the replicas) uploaded to this device
+    std::shared_ptr<const rg_host_tables> host;
+    std::vector<void *> allocations;
+    RgSph *sph = nullptr;
+    double *sph_cc = nullptr;
+    RgSphF *sphf = nullptr;
+    RgSphF2 *sphf2 = nullptr;
+    int32_t *sph_id = nullptr, *pln_id = nullptr, *dsk_id = nullptr, *box_id = nullptr;
+    RgPln *pln = nullptr;
+    RgDsk *dsk = nullptr;
+    RgBox *box = nullptr;
+    RgBodyDev *bodies = nullptr;
+    RgMatDev *mats = nullptr;
+    RgLightDev *lights = nullptr;
+    RgTexDev *texs = nullptr;
+    RgBvhNode *nodes = nullptr;     // sphere BVH (sphere tables are in its leaf order)
+    RgLightBufDev *lbuf = nullptr;  // shadow-ray light buffers (rg_lightbuf.cpp), n_lbuf lights
+    uint32_t *lb_start = nullptr, *lb_ent = nullptr;
+    uint32_t *shvol = nullptr;      // shadow mask volume of the PLAIN light kernels (rg_shadow_vol.cpp), null: none
+    std::vector<RgTexDev> tex_desc;  // the uploaded texture descriptors (device texel pointers)
+    // the LDS arena as one device image (RgKernelArgs::lds_blob), and the layout it was built for
+    void *lds_blob = nullptr;
+    rg_lds_layout lds_blob_layout{};
+    // The device table of the settings' light radii, which a band of a supersampled frame reads them from
+    // (RgKernelArgs::area_tab: every k's points, then the radii).  Unlike the camera and the lens the radii
+    // are as many as the scene has lights, so they travel by reference: the table is rewritten only with the
+    // device idle (rg_area_upload).  area_stale: the host radii are newer than the table (a replica, whose
+    // table is made when a frame first needs it).
+    bool area_stale = false;
+    double *d_area = nullptr;
+    // the ambient occlusion pass's table on the device (rg_ao.h RG_AO_TABLE_DOUBLES doubles: every k's points,
+    // then the lens's rotations): made on the first AO frame (rg_ao.hip), never rewritten
+    mutable double *d_ao = nullptr;
+    // Settings of the host-visible and multi-device paths, read on the root scene only (not synced to replicas):
+    int image_bands = 0;  // host-visible frames: 0 auto, -1 one launch writing host memory, -2 split, 1..16 row bands
+    int host_split_pct = 0;  // -2 (split): percent of the frame's rows rendered into device memory + DMA (0: default)
+    mutable int split_fail_a = 0;  // debug: the next N split renders report part A's launch as failed (rg_debug_fail_split_a)
     // rg_render_multi's automatic mode renders each light-scene device share as one launch (else bands + DMA)
     bool multi_light_one = RG_MULTI_LIGHT_ONE != 0;
     int host_tile_wlog = RG_HOST_TILE_WLOG;  // tile shape of the one-launch host-visible path
@@ -242,15 +226,11 @@ struct rg_scene {
     bool multi_stand_in = false;
     int multi_bands = 0;
     int multi_only_rank = -1;  // stand-in direct mode: issue only this device's work (timeline rehearsal)
-    std::shared_ptr<const rg_host_tables> host;
-    std::vector<RgTexDev> tex_desc;  // the uploaded texture descriptors (device texel pointers)
-    // the LDS arena as one device image (RgKernelArgs::lds_blob), for the layout it was built for
-    void *lds_blob = nullptr;
-    uint32_t lds_blob_layout[14] = {};
+    int aa_band_rows = 0;  // supersampled frames: output rows per band (rg_debug_set_aa_band_rows), 0 automatic
+    // resources, made on first use and reused across calls
     mutable std::vector<rg_launch_ctx *> ctxs;  // one per stream used
     mutable rg_launch_ctx *last = nullptr;       // the context of the latest launch (rg_debug_counters)
     mutable rg_image_res img;
-    int aa_band_rows = 0;  // supersampled frames: output rows per band (rg_debug_set_aa_band_rows), 0 automatic
     mutable rg_aa_res aa;
     mutable rg_multi_res *multi = nullptr;
     // frame pipelines built on this scene: a scene destroyed first detaches them
@@ -321,10 +301,11 @@ bool rg_host_is_pinned(const void *p, size_t bytes);
 // The device address of page-locked host memory [p, p + bytes) (nullptr: not pinned).
 void *rg_host_device_ptr(void *p, size_t bytes);
 
-// A copy of `src` on `device` (same tables, same settings).
+// A copy of `src` on `device`: its facts, its host tables uploaded there, its settings.
 rg_status rg_scene_replica(const rg_scene *src, int32_t device, rg_scene **out);
 void rg_scene_free(rg_scene *s);
-void rg_sync_settings(rg_scene *dst, const rg_scene *src);  // depth, path, BVH, lane depth, tile order
+// dst's settings become src's (every member of rg_scene_settings); changed light radii mark dst's area table stale.
+void rg_sync_settings(rg_scene *dst, const rg_scene *src);
 // The scene's area table (rg_area.h: the points, then s->light_radii) onto its device, made on first use.
 // Blocking: it waits for the device to go idle before it writes, so no launch in flight reads a torn table.
 rg_status rg_area_upload(rg_scene *s);
@@ -362,8 +343,8 @@ rg_status rg_grow(rg_mem kind, T *&p, size_t &cap, size_t bytes) {  // one buffe
 double rg_fov_adjustment(double fov);
 // rg_scene.hip: is the scene on the heavy path (rg_device.h rg_heavy_path)?
 bool rg_scene_heavy(const rg_scene *s);
-// rg_scene.hip: the LDS arena of launch args `a` as one device image (light path:
-// RgKernelArgs::lds_blob); nullptr if it cannot be made.
+// rg_scene.hip: the LDS arena of launch args `a` (made by rg_make_args) as one device image (light
+// path: RgKernelArgs::lds_blob), cached per layout; nullptr if it cannot be made.
 const void *rg_lds_blob_for(const rg_scene *s, const RgKernelArgs &a);
 
 // rg_capi.hip: tile shape (RgKernelArgs::tile_wlog) of the one-launch host-visible paths.

@@ -9,7 +9,10 @@
 //     (png_codec.cpp): the reference's textures and golden PNGs, then
 //     truncations and byte flips; PNG encode -> decode round trips;
 //   * the CPU restatement (oracle/raingun_oracle.c): a small render of every
-//     example scene through rgo_render (2 threads).
+//     example scene through rgo_render (2 threads);
+//   * the host scene builder (raingun_amd/csrc/rg_scene_build.cpp with the BVH, light-buffer and
+//     shadow-volume builders): every scene the loader accepts, fixture or corrupted, into host
+//     tables, then the LDS arena's layout and image with the BVH and the light buffers on and off.
 // Corrupted inputs may be rejected (any status); what must not happen is an
 // out-of-bounds access, use-after-free, leak or undefined behaviour -- the
 // sanitizers abort the process on the first one.
@@ -25,6 +28,7 @@
 
 #include "../../include/raingun.h"
 #include "../../include/raingun_host.h"
+#include "../../raingun_amd/csrc/rg_scene_tables.h"
 
 extern "C" int32_t rgo_render(const rg_scene_desc *s, uint32_t w, uint32_t h, const rg_tiling *tiling, uint8_t *rgba,
                               float *rgb, rg_ray_counts *counts, int32_t nthreads, int64_t *error_pixel);
@@ -70,6 +74,21 @@ int decode(const std::vector<uint8_t> &b, int flavor) {
     }
     rgh_free(px);
     return st;
+}
+
+// The scene builder on a description the loader accepted; any status is fine.  Returns the image bytes made.
+size_t build_scene(const rg_scene_desc *d) {
+    rg_host_tables h;
+    rg_scene_facts f;
+    if (rg_scene_build(d, h, f) != RG_OK) return 0;
+    std::vector<RgTexDev> texs(h.tex_w.size());
+    for (size_t i = 0; i < texs.size(); ++i) texs[i] = RgTexDev{h.texels[i].data(), (int32_t)h.tex_w[i], (int32_t)h.tex_h[i]};
+    size_t bytes = 0;
+    for (int mode = 0; mode < 4; ++mode) {
+        const rg_lds_layout L = rg_lds_layout_of(f, (mode & 1) != 0, (mode & 2) != 0, mode == 3 ? 6144u : 0u);
+        bytes += rg_lds_image(h, texs, L).size();
+    }
+    return bytes;
 }
 
 }  // namespace
@@ -142,6 +161,7 @@ int main(int argc, char **argv) {
         if (rgo_render(rgh_scene_desc(sc), W, H, &whole, rgba.data(), rgb.data(), &counts, 2, &err) != 0) return 8;
         rg_tiling shard = {5, 3, 1};  // a sharded tiling with a partial last tile
         if (rgo_render(rgh_scene_desc(sc), W, H, &shard, rgba.data(), nullptr, &counts, 2, &err) != 0) return 9;
+        if (build_scene(rgh_scene_desc(sc)) == 0) return 10;
         rgh_scene_free(sc);
         ++ok_files;
         mutate(y, n, 0xABCD ^ y.size(), [&](const std::vector<uint8_t> &x) {
@@ -150,6 +170,7 @@ int main(int argc, char **argv) {
             const int32_t st = rgh_scene_load_string((const char *)x.data(), x.size(), "/nonexistent", &m);
             if (st == 0) {
                 ++accepted;
+                (void)build_scene(rgh_scene_desc(m));
                 rgh_scene_free(m);
             } else {
                 ++rejected;

@@ -560,6 +560,44 @@ def test_render_multi_n_devices_stand_in(oracle_lib, example_scenes, mode, ngpus
     ds.close()
 
 
+def test_replica_follows_settings(example_scenes):
+    """A replica takes every member of rg_scene_settings from its root scene before each frame
+    (rg_sync_settings copies the struct whole): with the replicas made, each pixel-affecting setting is
+    changed on the root scene in turn, and the two-"device" frame must equal the one-device frame byte
+    for byte.  48 rows in tiles of 8 rows: three tile rows per device."""
+    from raingun_amd.camera import Camera
+
+    w, h, T = 64, 48, 8
+    ds = DeviceScene(example_scenes["test1"])
+    try:
+        ds.set_multi(0, stand_in=True, bands=0)
+        first = ds.render_multi(w, h, 2, T).copy()  # the replicas exist from here on
+        assert np.array_equal(first, ds.render_image(w, h))
+        # (a camera alone is also tests/test_gpu_camera.py::test_render_multi_stand_in; here it stays set
+        # while the other members change)
+        changes = [("max_depth 1", lambda: ds.set_max_depth(1)),
+                   ("camera", lambda: ds.set_camera(Camera.look_at((3, 2, -10), (0, 0, -30)))),
+                   ("path heavy", lambda: ds.set_path(_abi.PATH_HEAVY)),
+                   ("bvh off", lambda: ds.set_bvh(False)),
+                   ("light buffers off", lambda: ds.set_lightbuf(False)),
+                   ("shadow volume off", lambda: ds.set_shadow_volume(False)),
+                   ("first-hit tiles off", lambda: ds.set_first_hit_tiles(False)),
+                   ("exact division off", lambda: ds.set_exact_div(False))]
+        last = first
+        for what, change in changes:
+            change()
+            st_m, st_1 = _abi.rg_stats(), _abi.rg_stats()
+            multi = ds.render_multi(w, h, 2, T, stats=st_m).copy()
+            one = ds.render_image(w, h, stats=st_1)
+            assert np.array_equal(multi, one), (what, int((multi != one).any(axis=2).sum()))
+            assert st_m.rays.as_dict() == st_1.rays.as_dict(), what
+            if what in ("max_depth 1", "camera"):  # the setting took effect at all
+                assert not np.array_equal(multi, last), what
+            last = multi
+    finally:
+        ds.close()
+
+
 @pytest.mark.parametrize("flush,group", [(1, 1), (2, 2), (4, 1), (8, 3), (16, 16)])
 def test_light_host_ring_settings(oracle_lib, example_scenes, flush, group):
     """Round 6: the light path's LDS tile ring with a runtime flush size and queue group

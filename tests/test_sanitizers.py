@@ -1,7 +1,8 @@
 """Host-code sanitizers (CPU): the native host layer's parsers (YAML scene
-loader, JPEG decoder in both rounding flavours, PNG codec) and the CPU
-restatement, built with -fsanitize=address,undefined (leak checking on,
-every report fatal) and driven over the reference's fixtures and over
+loader, JPEG decoder in both rounding flavours, PNG codec), the CPU
+restatement and the host scene builder (rg_scene_build.cpp with the BVH,
+light-buffer and shadow-volume builders, on every scene the loader accepts),
+built with -fsanitize=address,undefined (leak checking on, every report fatal) and driven over the reference's fixtures and over
 truncated / byte-flipped copies of them (tests/native/sanitize_host.cpp).
 GPU code is out of reach: GPU AddressSanitizer is not available on this pool.
 """
@@ -26,6 +27,8 @@ def harness(tmp_path_factory):
     srcs = [REPO / "tests" / "native" / "sanitize_host.cpp"] + [HOST / f for f in
                                                                 ("yaml.cpp", "jpeg_decode.cpp", "png_codec.cpp",
                                                                  "scene_loader.cpp")]
+    srcs += [REPO / "raingun_amd" / "csrc" / f for f in ("rg_scene_build.cpp", "rg_bvh.cpp", "rg_lightbuf.cpp",
+                                                         "rg_shadow_vol.cpp")]
     subprocess.run(["g++", "-std=c++17", *SAN, "-c", *map(str, srcs)], cwd=d, check=True)
     subprocess.run(["gcc", "-std=c11", *SAN, "-c", str(REPO / "oracle" / "raingun_oracle.c")], cwd=d, check=True)
     exe = d / "sanitize_host"
