@@ -553,6 +553,93 @@ rg_status rg_render_ao_async(const rg_scene *scene, uint32_t width, uint32_t hei
                              const rg_ao *ao, float *ao_dev /* device, rg_tiling_rows x width */, void *stream,
                              rg_stats *stats);
 
+/* The edge-stopping filter of the AO pass: a tent over (2r+1) x (2r+1) pixels that takes in only neighbours on the
+ * same body whose normal agrees with the centre's.  The AO pass dithers by design (an integer count over k^2, turned
+ * per pixel); this is the geometry-aware filter that finishes it.  Its guides are the layers exactly as
+ * rg_render_aov delivers them (plane and disk normals are not unit).  No depth guide: all four body kinds are
+ * convex, so body and normal separate everything depth would.  Everything f32, unfused, in the order written.  Per
+ * pixel, row-major: `ao` (f32), `body` (i32, -1 on a miss), `normal` (3 x f32).  For pixel p = (x, y), b = body[p]:
+ *   b < 0:  out[p] = ao[p], bits unchanged.
+ *   else    nn_p = (n_p.x*n_p.x + n_p.y*n_p.y) + n_p.z*n_p.z;  t = normal_min * normal_min
+ *           sum = 0.0f;  wsum = 0 (an integer)
+ *           for dy = -r .. r (outer), dx = -r .. r (inner), q = (x + dx, y + dy); q outside the frame is skipped:
+ *               w = (r + 1 - |dx|) * (r + 1 - |dy|)                       a tent, an integer <= 81
+ *               d = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+ *               q is accepted iff it is the centre, or body[q] == b && d > 0.0f && d*d >= t * (nn_p * nn_q),
+ *               nn_q as nn_p; a NaN compares false
+ *               accepted:  sum = sum + (float)w * ao[q];  wsum += w
+ *           out[p] = sum / (float)wsum                                    wsum <= 6561; the centre makes it >= (r+1)^2
+ * The sum's order is part of the contract: the result is the same bits on every device and in
+ * raingun_amd/ambient.py's numpy restatement (filter_ao). */
+typedef struct rg_ao_filter_desc {
+    uint32_t radius;     /* r: 1..8 */
+    float normal_min;    /* in [0, 1]: the least cosine between the centre's normal and an accepted neighbour's */
+} rg_ao_filter_desc;
+
+/* The filter alone, on `device`, host buffers, blocking (as rg_resolve_box / rg_edge_mask): any shape, portrait
+ * too.  `ao_out` (width*height floats) may not alias `ao_in`.  RG_ERR_INVALID_ARGUMENT for null buffers, a null
+ * `filter`, zero sizes, 2^32 pixels or more, radius outside 1..8, normal_min NaN or outside [0, 1], or aliasing
+ * buffers, or a buffer that is not 4-byte aligned.  A rejected call writes nothing. */
+rg_status rg_ao_filter(int32_t device, const float *ao_in, const int32_t *body, const float *normal,
+                       uint32_t width, uint32_t height, const rg_ao_filter_desc *filter, float *ao_out);
+
+/* rg_ao_filter on device memory of `device` (4-byte aligned; nothing more is asked), enqueued on `stream` (a hipStream_t; NULL = null
+ * stream); asynchronous.  Same rejections. */
+rg_status rg_ao_filter_async(int32_t device, const float *ao_dev, const int32_t *body_dev, const float *normal_dev,
+                             uint32_t width, uint32_t height, const rg_ao_filter_desc *filter, float *ao_out_dev,
+                             void *stream);
+
+/* An ambient term: the filtered AO pass multiplied into an ambient light and added to the supersampled beauty frame.
+ * The reference has no ambient light, so what no light reaches renders black there; this is an addition, and colour
+ * (0, 0, 0) gives the bytes of rg_render_image_aa at the same `samples`.
+ *   share[b]  one f32 per body, from the scene description: diffuse: albedo; reflecting: (1.0f - reflectivity) *
+ *             albedo; refractive: 0.0f -- the weight get_color gives shade_diffuse (rendering.rs:86-118) times the
+ *             albedo of light_reflected (rendering.rs:165).  The AO pass is cosine-weighted, so the / pi of
+ *             light_reflected and the hemisphere's pi cancel: `color` means "this radiance from every open direction".
+ *   compose   per pixel p and channel c, f32, unfused:
+ *               hit (b = body[p] >= 0):  v = rgb[p].c + (color.c * albedo[p].c) * (share[b] * aof[p])
+ *               miss:                    v = rgb[p].c
+ *             then v clamped as a sample (v if 0 <= v <= 1, 1 if v > 1, else 0) and the byte `(v * 255.0) as u8`,
+ *             alpha 255: the rule of rg_render_image_aa's resolve.
+ *   rgb       the clamped f32 means of rg_render_aa_async at `samples`;  albedo, body: rg_render_aov's layers;
+ *   aof       rg_ao_filter{filter_radius, normal_min} of rg_render_ao{ao} guided by rg_render_aov's body and normal,
+ *             or the raw pass when filter_radius is 0.
+ * The camera, the lens and the light radii are honoured because the passes honour them (the AOV and AO passes trace
+ * the pinhole ray of the pixel's centre).  There is no adaptive variant, and rg_render_multi and rg_frames_* have no
+ * ambient mode. */
+typedef struct rg_ambient {
+    float color[3];          /* finite, >= 0 */
+    uint32_t samples;        /* the beauty frame's samples per pixel side, 1..8 */
+    rg_ao ao;
+    uint32_t filter_radius;  /* 0..8; 0: unfiltered */
+    float normal_min;        /* in [0, 1] */
+} rg_ambient;
+
+/* Blocking whole frame with an ambient term into host buffers: `rgba_out` width*height*4 bytes; `rgb_out` (nullable)
+ * width*height*3 floats, the clamped v; `ao_out` (nullable) width*height floats, aof.  On the scene's device it runs,
+ * in order, the supersampled beauty frame, the AOV pass (body, normal, albedo), the AO pass, the filter and the
+ * compose, then copies out.  `stats` (nullable) is the sum of the three tracing passes: primary == pixels x
+ * (samples^2 + 2), shadow == the beauty frame's + k^2 x hit pixels, secondary == the beauty frame's; kernel_ms adds the
+ * three passes' and the two image kernels'.  On a device error (the reference's panics) the frame is still delivered,
+ * error_pixel is the lowest failing pixel over the three passes and the status that pixel's; a tie goes to the beauty
+ * frame, then the AOV pass, then the AO pass.  RG_ERR_PORTRAIT for width < height; RG_ERR_INVALID_ARGUMENT for null
+ * `scene`, `ambient` or `rgba_out`, zero sizes, a sample frame of 2^32 pixels or more, a colour that is negative or
+ * not finite, samples outside 1..8, an `ao` rg_render_ao rejects, filter_radius above 8, normal_min NaN or outside
+ * [0, 1].  A rejected call writes nothing. */
+rg_status rg_render_image_ambient(const rg_scene *scene, uint32_t width, uint32_t height, const rg_ambient *ambient,
+                                  uint8_t *rgba_out, float *rgb_out, float *ao_out, rg_stats *stats);
+
+/* Device-resident rg_render_image_ambient: `rgba_dev`, `rgb_dev` (nullable) and `ao_dev` (nullable) are device
+ * pointers on the scene's device, each 4-byte aligned (`rgba_dev` too: the compose stores whole pixels;
+ * RG_ERR_INVALID_ARGUMENT otherwise).  The work is ordered after everything enqueued on `stream` so far and later work on
+ * `stream` after it (the beauty frame runs as rg_render_aa_async does); the layers between the passes live in
+ * scratch the scene keeps per stream, so frames on distinct streams may be in flight together.  Asynchronous unless
+ * `stats` is non-NULL: then every tracing pass synchronises `stream`.  Without `stats` the beauty frame's device
+ * errors are not reported (rg_stream_status sees the AOV and AO passes).  Calls on one scene must come from one host
+ * thread at a time. */
+rg_status rg_render_ambient_async(const rg_scene *scene, uint32_t width, uint32_t height, const rg_ambient *ambient,
+                                  uint8_t *rgba_dev, float *rgb_dev, float *ao_dev, void *stream, rg_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,15 @@ class rg_ao(C.Structure):  # the ambient occlusion pass, by value (include/raing
     _fields_ = [("samples", C.c_uint32), ("_pad", C.c_uint32), ("radius", C.c_double), ("bias", C.c_double)]
 
 
+class rg_ao_filter_desc(C.Structure):  # the AO pass's edge-stopping filter, by value (include/raingun.h)
+    _fields_ = [("radius", C.c_uint32), ("normal_min", C.c_float)]
+
+
+class rg_ambient(C.Structure):  # an ambient term, by value (include/raingun.h)
+    _fields_ = [("color", C.c_float * 3), ("samples", C.c_uint32), ("ao", rg_ao), ("filter_radius", C.c_uint32),
+                ("normal_min", C.c_float)]
+
+
 class rg_lens(C.Structure):
     _fields_ = [("aperture", C.c_double), ("focus", C.c_double)]
 
@@ -177,6 +186,10 @@ EXPORTED_SYMBOLS = (
     "rg_ao_tables",
     "rg_render_ao",
     "rg_render_ao_async",
+    "rg_ao_filter",
+    "rg_ao_filter_async",
+    "rg_render_image_ambient",
+    "rg_render_ambient_async",
 )
 # include/raingun_debug.h
 DEBUG_SYMBOLS = ("rg_debug_set_path", "rg_debug_set_bvh", "rg_debug_bvh_info", "rg_debug_counters",
@@ -374,6 +387,19 @@ def _declare(lib: C.CDLL) -> None:
         lib.rg_render_ao_async.restype = C.c_int32
         lib.rg_render_ao_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_tiling), P(rg_ao), C.c_void_p,
                                            C.c_void_p, P(rg_stats)]
+    if hasattr(lib, "rg_render_image_ambient"):  # absent from older builds A/B runs load (RAINGUN_HIP_LIB)
+        lib.rg_ao_filter.restype = C.c_int32
+        lib.rg_ao_filter.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                     P(rg_ao_filter_desc), C.c_void_p]
+        lib.rg_ao_filter_async.restype = C.c_int32
+        lib.rg_ao_filter_async.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                           P(rg_ao_filter_desc), C.c_void_p, C.c_void_p]
+        lib.rg_render_image_ambient.restype = C.c_int32
+        lib.rg_render_image_ambient.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_ambient), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, P(rg_stats)]
+        lib.rg_render_ambient_async.restype = C.c_int32
+        lib.rg_render_ambient_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(rg_ambient), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, P(rg_stats)]
     lib.rg_frames_status.restype = C.c_int32
     lib.rg_frames_status.argtypes = [C.c_void_p, P(C.c_int32)]
     if hasattr(lib, "rg_frames_set_batch"):  # absent from pre-round-3 builds

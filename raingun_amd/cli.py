@@ -2,7 +2,8 @@
 
     python -m raingun_amd.cli [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
                               [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D]
-                              [--light-radius R[,R...]] [--aov LAYERS] [--ao K[,RADIUS[,BIAS]]] [-o FILE] FILE
+                              [--light-radius R[,R...]] [--aov LAYERS] [--ao K[,RADIUS[,BIAS]]]
+                              [--ambient R,G,B] [--ao-filter R[,NMIN]] [-o FILE] FILE
 
 Flags and their precedence follow construct_app / RenderOptions::from
 (main.rs:21-96): --draft forces 800x600 and caps the recursion depth at 4
@@ -41,7 +42,17 @@ occlusion of the frame (rg_render_ao), K x K rays over the hemisphere above
 each pixel's primary hit, as the grey picture of raingun_amd/ao.py visualize.
 It honours the size flags and the camera and is independent of --samples,
 --aperture and --light-radius; it runs after the beauty frame and outside its
-timing line.  Without --ao nothing changes.  The
+timing line.  Without --ao nothing changes.
+`--ambient R,G,B` (or one number for grey; not in the reference, which has no
+ambient light) makes `out.png` the frame of rg_render_image_ambient: the
+--samples frame plus this radiance from every open direction, weighted by the
+filtered AO pass (raingun_amd/ambient.py).  It needs --ao, refuses --adaptive
+and combines with --samples, the camera, the lens and --light-radius.
+`--ao-filter R[,NMIN]` (R 0..8, NMIN in [0, 1], default 0.9) is the
+edge-stopping filter of the AO pass (rg_ao_filter); it needs --ao.  With
+--ambient the default is 2,0.9 and `--ao-filter 0` composes the raw pass; given
+explicitly, `out.ao.png` shows the filtered pass.  Without the two flags
+nothing changes.  The
 render itself runs on the GPU (rg_render_image); the scene is loaded and the
 PNG written by the native host layer (libraingun_host.so), and the timing line matches
 print_render_message (render.rs:218-244).  `--preview` (piston window) is not
@@ -58,7 +69,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import ao, aov
+from . import ambient, ao, aov
 from .camera import (Camera, Lens, camera_from_flags, lens_from_flags, light_radii_from_flags, parse_triple,
                      spread_light_radii)
 
@@ -75,6 +86,8 @@ class RenderOptions:          # render.rs:32-46
     light_radii: Optional[tuple] = None  # --light-radius as given: one number or one per light (not in the reference)
     aov: tuple = ()           # layers of --aov, in aov.LAYERS order (not in the reference)
     ao: Optional[tuple] = None  # --ao as (samples, radius, bias) (not in the reference)
+    ambient: Optional[tuple] = None  # --ambient as (r, g, b) (not in the reference)
+    ao_filter: Optional[tuple] = None  # --ao-filter as (radius, normal_min), None: not given (not in the reference)
 
 
 class _LastWins(argparse.Action):
@@ -120,6 +133,12 @@ def construct_app() -> argparse.ArgumentParser:  # main.rs:21-68
     p.add_argument("--ao", metavar="K[,RADIUS[,BIAS]]",
                    help="Also write FILENAME.ao.png: ambient occlusion from K x K rays per pixel (K 1..8) that "
                         "hits within RADIUS occlude (default inf), leaving BIAS above the surface (default 1e-13).")
+    p.add_argument("--ambient", metavar="R,G,B",
+                   help="Ambient light of this colour (or one number for grey), weighted by the filtered --ao pass, "
+                        "added to the frame.")
+    p.add_argument("--ao-filter", dest="ao_filter", metavar="R[,NMIN]",
+                   help="Edge-stopping filter of the --ao pass: radius 0..8 (0: off) and the least normal cosine "
+                        "(default 0.9); with --ambient the default is 2,0.9.")
     p.add_argument("input", metavar="FILE", help="The scene definition file, in YAML format.")
     return p
 
@@ -153,6 +172,22 @@ def options_from(ns: argparse.Namespace) -> RenderOptions:  # main.rs:70-96
             o.ao = ao.parse_spec(ns.ao)
         except ValueError:
             raise SystemExit("Could not parse ao") from None
+    if ns.ambient is not None:
+        try:
+            o.ambient = ambient.parse_spec(ns.ambient)
+        except ValueError:
+            raise SystemExit("Could not parse ambient") from None
+        if o.ao is None:
+            raise SystemExit("ambient needs ao")
+        if o.adaptive is not None:
+            raise SystemExit("ambient cannot be used with adaptive")
+    if ns.ao_filter is not None:
+        try:
+            o.ao_filter = ambient.parse_filter_spec(ns.ao_filter)
+        except ValueError:
+            raise SystemExit("Could not parse ao-filter") from None
+        if o.ao is None:
+            raise SystemExit("ao-filter needs ao")
     if ns.draft:
         o.max_recursion_depth = 4
     elif ns.hd:
@@ -265,8 +300,13 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
             ds.set_light_radii(spread_light_radii(opts.light_radii, [isinstance(l, SphericalLight) for l in scene.lights]))
         except ValueError as e:
             raise SystemExit(f"Could not build the area lights: {e}") from None
+    occlusion = None  # --ambient: the pass it composed (filtered, or raw at --ao-filter 0)
     t0 = time.perf_counter()                     # render.rs:54-56
-    if opts.samples > 1 and opts.adaptive is not None:
+    if opts.ambient is not None:
+        radius, normal_min = opts.ao_filter if opts.ao_filter is not None else ambient.DEFAULT_FILTER
+        img, occlusion = ds.render_ambient(opts.width, opts.height, opts.ambient, *opts.ao, samples=opts.samples,
+                                           filter_radius=radius, normal_min=normal_min, want_ao=True)
+    elif opts.samples > 1 and opts.adaptive is not None:
         img = ds.render_image_aa_adaptive(opts.width, opts.height, opts.samples, opts.adaptive)
     elif opts.samples > 1:
         img = ds.render_image_aa(opts.width, opts.height, opts.samples)
@@ -280,7 +320,11 @@ def main(argv: Optional[List[str]] = None) -> int:  # main.rs:98-132
         for name in opts.aov:
             output_path.with_suffix(f".{name}.png").write_bytes(encode_png(aov.visualize(name, layers[name])))
     if opts.ao is not None:  # out.png -> out.ao.png, whatever --samples, --aperture and --light-radius say
-        occlusion = ds.render_ao(opts.width, opts.height, *opts.ao)
+        if opts.ambient is None or opts.ao_filter is None:  # the raw pass; else the pass --ambient composed
+            occlusion = ds.render_ao(opts.width, opts.height, *opts.ao)
+        if opts.ambient is None and opts.ao_filter is not None and opts.ao_filter[0] > 0:  # the filtered pass
+            guides = ds.render_aov(opts.width, opts.height, ("body", "normal"))
+            occlusion = ds.filter_ao(occlusion, guides["body"], guides["normal"], *opts.ao_filter)
         output_path.with_suffix(".ao.png").write_bytes(encode_png(ao.visualize(occlusion)))
     ds.close()
     print(f"{input_path}\t→\t{output_path}\t({format_duration(int((t1 - t0) * 1000))} render, "

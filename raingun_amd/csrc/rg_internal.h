@@ -2,7 +2,7 @@
 // determines is in rg_scene_tables.h, built without a device by rg_scene_build.cpp), shared
 // by rg_scene.hip (scene upload, replicas, kernel arguments), rg_launch.hip (per-stream
 // launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
-// streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_ao.hip (the ambient occlusion pass), rg_frames.hip
+// streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_ao.hip (the ambient occlusion pass), rg_ambient.hip (the ambient term), rg_frames.hip
 // (frames in flight over N processes), rg_multi.hip (one process driving N
 // devices), rg_gather.hip (the pack and re-interleave kernels of both) and rg_rccl.hip
 // (the run-time RCCL loader, rg_rccl.h, and the rg_comm_* functions).  The band resource
@@ -141,6 +141,16 @@ struct rg_aa_res : rg_band_res {
     double *d_lens = nullptr;
 };
 
+// Resources of the ambient frames (rg_render_ambient_async, rg_ambient.hip), one set per stream used: the layers
+// between the passes (f32 rgb, albedo, normal; body; the raw and the filtered AO pass) in one allocation, and
+// the events around the two image kernels.
+struct rg_ambient_res {
+    hipStream_t stream = nullptr;
+    void *mem = nullptr;
+    size_t cap = 0;  // bytes
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
 struct rg_multi_res;  // rg_multi.hip
 struct rg_frames;     // rg_frames.hip (include/raingun_frames.h)
 
@@ -211,6 +221,9 @@ struct rg_scene : rg_scene_facts, rg_scene_settings {
     // the ambient occlusion pass's table on the device (rg_ao.h RG_AO_TABLE_DOUBLES doubles: every k's points,
     // then the lens's rotations): made on the first AO frame (rg_ao.hip), never rewritten
     mutable double *d_ao = nullptr;
+    // the ambient term's share per body on the device (host->amb_share): made on the first ambient frame
+    // (rg_ambient.hip), never rewritten
+    mutable float *d_share = nullptr;
     // Settings of the host-visible and multi-device paths, read on the root scene only (not synced to replicas):
     int image_bands = 0;  // host-visible frames: 0 auto, -1 one launch writing host memory, -2 split, 1..16 row bands
     int host_split_pct = 0;  // -2 (split): percent of the frame's rows rendered into device memory + DMA (0: default)
@@ -232,6 +245,7 @@ struct rg_scene : rg_scene_facts, rg_scene_settings {
     mutable rg_launch_ctx *last = nullptr;       // the context of the latest launch (rg_debug_counters)
     mutable rg_image_res img;
     mutable rg_aa_res aa;
+    mutable std::vector<rg_ambient_res> amb;  // one per stream used
     mutable rg_multi_res *multi = nullptr;
     // frame pipelines built on this scene: a scene destroyed first detaches them
     // (rg_frames_destroy then no longer touches it), in either destruction order
@@ -353,6 +367,9 @@ uint32_t rg_host_tile_wlog(const rg_scene *s);
 void rg_image_res_release(rg_image_res &r);
 // rg_aa.hip: free the supersampled paths' resources.
 void rg_aa_res_release(rg_aa_res &r);
+
+// rg_ambient.hip: free the ambient frames' resources of `stream`, or of every stream (all).
+void rg_ambient_release(const rg_scene *s, hipStream_t stream, bool all);
 
 // rg_gather.hip: pack npx RGBA pixels to RGB (3 B per pixel), as a part travels in a gather.
 hipError_t rg_launch_pack_rgb(const void *rgba, void *rgb, size_t npx, hipStream_t stream);

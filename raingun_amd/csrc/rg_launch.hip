@@ -420,6 +420,7 @@ rg_status rg_scene_release_stream(rg_scene *s, void *stream) {
     hipStream_t hs = static_cast<hipStream_t>(stream);
     if (!hs) return RG_OK;  // the null-stream context lives as long as the scene
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
+    rg_ambient_release(s, hs, false);
     for (size_t i = 0; i < s->ctxs.size(); ++i) {
         if (s->ctxs[i]->stream != hs) continue;
         rg_launch_ctx *c = s->ctxs[i];

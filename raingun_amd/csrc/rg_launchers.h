@@ -43,6 +43,19 @@ struct RgAoArgs {
     double radius, bias;
 };
 extern "C" hipError_t rg_launch_ao(const RgKernelArgs *a, const RgAoArgs *o, hipStream_t stream);
+// rg_ao_filter.hip: the edge-stopping filter of the AO pass (rg_ao_filter of include/raingun.h; rg_ambient.h) over
+// a width x height frame in device memory: ao, body, out one element per pixel, normal three; out may not alias
+// ao.  hipErrorInvalidValue for a null pointer, a zero size, radius outside 1 .. 8 or normal_min outside [0, 1].
+extern "C" hipError_t rg_launch_ao_filter(const float *ao, const int32_t *body, const float *normal, uint32_t width,
+                                          uint32_t height, uint32_t radius, float normal_min, float *out,
+                                          hipStream_t stream);
+// rg_ao_filter.hip: the ambient term added to npx pixels (rg_render_image_ambient's compose): rgb, albedo three
+// floats per pixel, body, aof one; share: n_share floats, one per body (a body id outside the table composes as a
+// miss); rgba npx RGBA8 pixels; rgb_out (nullable, may be rgb): the clamped sums.
+extern "C" hipError_t rg_launch_ambient_compose(const float *rgb, const float *albedo, const int32_t *body,
+                                                const float *aof, const float *share, uint32_t n_share,
+                                                const float color[3], unsigned long long npx, uint8_t *rgba,
+                                                float *rgb_out, hipStream_t stream);
 // rg_kernels.hip: *bad (device, zeroed by the caller) += the pixels of the a->width x a->height frame whose
 // camera direction differs between the general and the PLAIN kernels' arithmetic (rg_debug_camera_check).
 extern "C" hipError_t rg_launch_camera_check(const RgKernelArgs *a, unsigned long long *bad, hipStream_t stream);

@@ -50,6 +50,9 @@ void release(rg_scene *s) {
     s->allocations.clear();
     if (s->d_ao) (void)hipFree(s->d_ao);
     s->d_ao = nullptr;
+    rg_ambient_release(s, nullptr, true);
+    if (s->d_share) (void)hipFree(s->d_share);
+    s->d_share = nullptr;
     if (s->lds_blob) (void)hipFree(s->lds_blob);
     s->lds_blob = nullptr;
     for (rg_launch_ctx *c : s->ctxs) rg_ctx_destroy(c);

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "rg_ambient.h"
 #include "rg_bvh.h"
 #include "rg_exact.h"
 #include "rg_lightbuf.h"
@@ -108,6 +109,7 @@ rg_status rg_scene_build(const rg_scene_desc *d, rg_host_tables &h, rg_scene_fac
     std::vector<double> sp;  // centre xyz, radius by sphere-table position (the builders' input)
     h.bodies.resize(d->n_bodies);
     h.mats.resize(d->n_bodies);
+    h.amb_share.resize(d->n_bodies);
     for (uint32_t i = 0; i < d->n_bodies; ++i) {
         const rg_body &b = d->bodies[i];
         const double *p = b.p;
@@ -126,6 +128,7 @@ rg_status rg_scene_build(const rg_scene_desc *d, rg_host_tables &h, rg_scene_fac
         md.reflectivity = m.reflectivity;
         md.index = m.index;
         md.transparency = m.transparency;
+        h.amb_share[i] = rg_ambient_share(m.surface, m.albedo, m.reflectivity);
         switch (b.kind) {
         case RG_BODY_SPHERE:
             // r2 = radius * radius and cc = (c.c) evaluated exactly as the per-ray

@@ -31,6 +31,7 @@ struct rg_host_tables {
     std::vector<uint32_t> shvol;               // the shadow mask volume's words (rg_shadow_vol.h), empty: none
     std::vector<uint32_t> tex_w, tex_h;
     std::vector<std::vector<uint32_t>> texels;
+    std::vector<float> amb_share;              // per body, YAML order: the ambient term's share (rg_ambient.h rg_ambient_share)
 };
 
 // The scalars the description determines: a replica shares them with its root scene, whole

@@ -4,8 +4,15 @@
 //
 //   raingun [-w PIXELS] [-h PIXELS] [--4k|--hd] [--draft] [--samples N] [--adaptive T]
 //           [--eye X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z] [--aperture R --focus D] [--light-radius R[,R...]]
-//           [--aov LAYERS] [--ao K[,RADIUS[,BIAS]]] [-o FILE] [--gpu N] FILE
+//           [--aov LAYERS] [--ao K[,RADIUS[,BIAS]]] [--ambient R,G,B] [--ao-filter R[,NMIN]] [-o FILE] [--gpu N] FILE
 //
+// --ambient R,G,B (or one number for grey; not in the reference, which has no ambient light): `out.png` becomes
+// the frame of rg_render_image_ambient -- the --samples frame plus this radiance from every open direction, weighted
+// by the filtered AO pass.  It needs --ao, refuses --adaptive, and combines with --samples, the camera, the lens and
+// --light-radius.  A colour that is negative or not finite is an argument error.
+// --ao-filter R[,NMIN] (R 0..8, NMIN in [0, 1], default 0.9): the edge-stopping filter of the AO pass
+// (rg_ao_filter).  It needs --ao.  With --ambient the default is 2,0.9 and `--ao-filter 0` composes the raw pass;
+// given explicitly, `out.ao.png` shows the filtered pass (without the flag it stays the raw one).
 // --ao K[,RADIUS[,BIAS]] (not in the reference): next to `-o out.png` the run also writes `out.ao.png`, the
 // ambient occlusion of the frame (rg_render_ao): K x K rays (K 1..8) over the hemisphere above each pixel's
 // primary hit, occluded by hits within RADIUS (> 0, `inf` the default), leaving BIAS (>= 0, default 1e-13)
@@ -75,6 +82,8 @@ const char *kHelp =
     "        --aperture <R>         Lens radius in world units (with --focus and --samples 2 or more).\n"
     "        --focus <D>            Distance of the plane in focus, in lengths of the forward vector.\n"
     "        --light-radius <R>     Radius of every spherical light in world units, or R,R,.. one per light (with --samples 2 or more).\n"
+    "        --ambient <R,G,B>      Ambient light of this colour (or one number), weighted by the filtered --ao pass, added to the frame.\n"
+    "        --ao-filter <R[,NMIN]> Edge-stopping filter of the --ao pass: radius 0..8 (0: off), least normal cosine (default 0.9); with --ambient the default is 2,0.9.\n"
     "        --ao <K[,RADIUS[,BIAS]]>  Also write FILENAME.ao.png: ambient occlusion, K x K rays per pixel (1..8), hits within RADIUS occlude (default inf).\n"
     "        --aov <LAYERS>         Also write FILENAME.<layer>.png for each of body,depth,normal,uv,albedo (or all).\n"
     "        --adaptive <T>         Adaptive anti-aliasing: the N x N rays only where the 1-sample frame's contrast is at least T (0..256).\n"
@@ -100,7 +109,7 @@ const char *kHelp =
 struct Args {
     bool draft = false, hd = false, uhd = false, preview = false;
     const char *width = nullptr, *height = nullptr, *output = nullptr, *input = nullptr, *samples = nullptr,
-               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr, *ao = nullptr, *aperture = nullptr, *focus = nullptr,
+               *adaptive = nullptr, *eye = nullptr, *look_at = nullptr, *up = nullptr, *aov = nullptr, *ao = nullptr, *ambient = nullptr, *ao_filter = nullptr, *aperture = nullptr, *focus = nullptr,
                *light_radius = nullptr;
     int gpu = 0;
 };
@@ -121,6 +130,10 @@ struct RenderOptions {  // render.rs:32-46
     bool any_aov = false;
     bool has_ao = false;  // --ao
     rg_ao ao{1, 0, INFINITY, 1e-13};
+    bool has_ambient = false;  // --ambient
+    float ambient[3] = {0.0f, 0.0f, 0.0f};
+    bool has_filter = false;  // --ao-filter given explicitly
+    rg_ao_filter_desc filter{0, 0.9f};  // radius 0: no filter (with --ambient and no --ao-filter: 2, 0.9)
 };
 
 const char *const kLayers[5] = {"body", "depth", "normal", "uv", "albedo"};
@@ -191,6 +204,8 @@ Args parse_args(int argc, char **argv) {
             else if (name == "look-at") a.look_at = take_value(i, "--look-at <X,Y,Z>", val);
             else if (name == "up") a.up = take_value(i, "--up <X,Y,Z>", val);
             else if (name == "ao") a.ao = take_value(i, "--ao <K[,RADIUS[,BIAS]]>", val);
+            else if (name == "ambient") a.ambient = take_value(i, "--ambient <R,G,B>", val);
+            else if (name == "ao-filter") a.ao_filter = take_value(i, "--ao-filter <R[,NMIN]>", val);
             else if (name == "aov") a.aov = take_value(i, "--aov <LAYERS>", val);
             else if (name == "aperture") a.aperture = take_value(i, "--aperture <R>", val);
             else if (name == "focus") a.focus = take_value(i, "--focus <D>", val);
@@ -266,6 +281,50 @@ RenderOptions options_from(const Args &a) {  // main.rs:70-96
         if (good && parts.size() > 2) good = number(parts[2], &o.ao.bias) && o.ao.bias - o.ao.bias == 0.0 && o.ao.bias >= 0.0;
         if (!good) clap_error(std::string("Invalid value for '--ao <K[,RADIUS[,BIAS]]>': ") + a.ao);
         o.has_ao = true;
+    }
+    auto split = [](const std::string &spec) {
+        std::vector<std::string> parts;
+        for (size_t pos = 0;;) {
+            const size_t comma = spec.find(',', pos);
+            parts.push_back(spec.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos));
+            if (comma == std::string::npos) break;
+            pos = comma + 1;
+        }
+        return parts;
+    };
+    // a number of --ambient / --ao-filter: decimal digits, '.', an exponent and signs only (no hex floats, no inf or
+    // nan: what raingun_amd/ambient.py accepts), and within f32's range
+    auto decimal = [](const std::string &t, double *out) {
+        if (t.empty() || t.find_first_not_of("0123456789.eE+-") != std::string::npos) return false;
+        return parse_f64(t.c_str(), out) && std::fabs(*out) <= 3.4028234663852886e38;
+    };
+    if (a.ambient) {  // R,G,B or one number: finite, >= 0 as f32
+        const std::vector<std::string> parts = split(a.ambient);
+        bool good = parts.size() == 1 || parts.size() == 3;
+        for (size_t k = 0; good && k < parts.size(); ++k) {
+            double v = 0.0;
+            good = decimal(parts[k], &v);
+            const float f = good ? (float)v : 0.0f;
+            good = good && f >= 0.0f;
+            if (parts.size() == 1) o.ambient[0] = o.ambient[1] = o.ambient[2] = f;
+            else o.ambient[k] = f;
+        }
+        if (!good) clap_error(std::string("Invalid value for '--ambient <R,G,B>': ") + a.ambient);
+        if (!o.has_ao) clap_error("The argument '--ambient <R,G,B>' needs '--ao <K[,RADIUS[,BIAS]]>'");
+        if (o.has_adaptive) clap_error("The argument '--ambient <R,G,B>' cannot be used with '--adaptive <T>'");
+        o.has_ambient = true;
+        o.filter.radius = 2;
+    }
+    if (a.ao_filter) {  // R[,NMIN]: R 0..8; NMIN in [0, 1] as f32
+        const std::vector<std::string> parts = split(a.ao_filter);
+        double nmin = 0.9;
+        bool good = parts.size() >= 1 && parts.size() <= 2 && parse_u32(parts[0].c_str(), &o.filter.radius) && o.filter.radius <= 8;
+        if (good && parts.size() > 1) good = decimal(parts[1], &nmin);
+        o.filter.normal_min = good ? (float)nmin : 0.0f;
+        good = good && o.filter.normal_min >= 0.0f && o.filter.normal_min <= 1.0f;
+        if (!good) clap_error(std::string("Invalid value for '--ao-filter <R[,NMIN]>': ") + a.ao_filter);
+        if (!o.has_ao) clap_error("The argument '--ao-filter <R[,NMIN]>' needs '--ao <K[,RADIUS[,BIAS]]>'");
+        o.has_filter = true;
     }
     if (a.up && !a.look_at) clap_error("The argument '--up <X,Y,Z>' needs '--look-at <X,Y,Z>'");
     if (a.eye || a.look_at) {
@@ -453,8 +512,20 @@ int main(int argc, char **argv) {
     }
     std::vector<uint8_t> rgba((size_t)opts.width * opts.height * 4);
 
+    std::vector<float> occlusion;  // --ambient: the pass it composed (filtered, or raw at --ao-filter 0)
+    rg_ambient term{};
+    if (opts.has_ambient) {
+        for (int c = 0; c < 3; ++c) term.color[c] = opts.ambient[c];
+        term.samples = opts.samples;
+        term.ao = opts.ao;
+        term.filter_radius = opts.filter.radius;
+        term.normal_min = opts.filter.normal_min;
+        occlusion.resize((size_t)opts.width * opts.height);
+    }
     auto t0 = std::chrono::steady_clock::now();  // render.rs:54-56
-    st = opts.samples > 1 && opts.has_adaptive
+    st = opts.has_ambient
+             ? rg_render_image_ambient(scene, opts.width, opts.height, &term, rgba.data(), nullptr, occlusion.data(), nullptr)
+         : opts.samples > 1 && opts.has_adaptive
              ? rg_render_image_aa_adaptive(scene, opts.width, opts.height, opts.samples, opts.adaptive, rgba.data(), nullptr,
                                            nullptr, nullptr)
          : opts.samples > 1 ? rg_render_image_aa(scene, opts.width, opts.height, opts.samples, rgba.data(), nullptr, nullptr)
@@ -484,9 +555,21 @@ int main(int argc, char **argv) {
     }
     if (opts.has_ao) {  // after the beauty frame and outside its timing line
         const size_t n = (size_t)opts.width * opts.height;
-        std::vector<float> occlusion(n);
-        st = rg_render_ao(scene, opts.width, opts.height, &opts.ao, occlusion.data(), nullptr);
-        if (st != RG_OK) panic(rg_status_string(st));
+        if (!(opts.has_ambient && opts.has_filter)) {  // the raw pass; else the pass --ambient composed
+            occlusion.resize(n);
+            st = rg_render_ao(scene, opts.width, opts.height, &opts.ao, occlusion.data(), nullptr);
+            if (st != RG_OK) panic(rg_status_string(st));
+        }
+        if (!opts.has_ambient && opts.has_filter && opts.filter.radius > 0) {  // --ao-filter alone: the filtered pass
+            std::vector<int32_t> body(n);
+            std::vector<float> normal(3 * n), raw(occlusion);
+            const rg_aov guides = {body.data(), nullptr, normal.data(), nullptr, nullptr};
+            st = rg_render_aov(scene, opts.width, opts.height, &guides, nullptr);
+            if (st == RG_OK)
+                st = rg_ao_filter(args.gpu, raw.data(), body.data(), normal.data(), opts.width, opts.height, &opts.filter,
+                                  occlusion.data());
+            if (st != RG_OK) panic(rg_status_string(st));
+        }
         for (size_t i = 0; i < n; ++i) {  // raingun_amd/ao.py visualize
             uint8_t *p = rgba.data() + 4 * i;
             p[0] = p[1] = p[2] = f32_to_u8(occlusion[i] * 255.0f);

@@ -621,6 +621,45 @@ class DeviceScene:
         _abi.check(status, "rg_render_ao_async")
         return out
 
+    def filter_ao(self, ao_in: np.ndarray, body: np.ndarray, normal: np.ndarray, radius: int = 2,
+                  normal_min: float = 0.9) -> np.ndarray:
+        """rg_ao_filter on this scene's device: the edge-stopping tent filter of an AO pass, guided by the AOV
+        pass's body and normal layers (raingun_amd/ambient.py filter_ao states it).  (H, W) float32, (H, W)
+        int32, (H, W, 3) float32 -> (H, W) float32; any shape."""
+        a = np.ascontiguousarray(ao_in, dtype=np.float32)
+        b = np.ascontiguousarray(body, dtype=np.int32)
+        n = np.ascontiguousarray(normal, dtype=np.float32)
+        if a.ndim != 2 or a.size == 0 or b.shape != a.shape or n.shape != (*a.shape, 3):
+            raise ValueError("expected ao (H, W), body (H, W) and normal (H, W, 3)")
+        h, w = a.shape
+        out = np.empty((h, w), dtype=np.float32)
+        f = _abi.rg_ao_filter_desc(int(radius), float(normal_min))
+        _abi.check(_abi.lib().rg_ao_filter(int(self.device), a.ctypes.data, b.ctypes.data, n.ctypes.data, w, h,
+                                           C.byref(f), out.ctypes.data), "rg_ao_filter")
+        return out
+
+    def render_ambient(self, width: int, height: int, color, ao_samples: int, ao_radius: float = float("inf"),
+                       ao_bias: float = 1e-13, samples: int = 1, filter_radius: int = 2, normal_min: float = 0.9,
+                       want_rgb: bool = False, want_ao: bool = False, stats: Optional[_abi.rg_stats] = None):
+        """rg_render_image_ambient: the samples x samples supersampled frame plus an ambient light of `color`
+        (three floats, or one for grey) weighted by the filtered AO pass (raingun_amd/ambient.py states the
+        filter and the compose).  filter_radius 0: the raw pass.  Returns the (H, W, 4) uint8 frame, followed by
+        the (H, W, 3) float32 composed colours with want_rgb and by the (H, W) float32 filtered pass with
+        want_ao.  A device error raises RaingunError; `stats` then names the first failing pixel."""
+        col = np.broadcast_to(np.asarray(color, dtype=np.float32).reshape(-1), (3,))
+        out = np.empty((height, width, 4), dtype=np.uint8)
+        rgb = np.empty((height, width, 3), dtype=np.float32) if want_rgb else None
+        aof = np.empty((height, width), dtype=np.float32) if want_ao else None
+        m = _abi.rg_ambient((C.c_float * 3)(*[float(c) for c in col]), int(samples),
+                            _abi.rg_ao(int(ao_samples), 0, float(ao_radius), float(ao_bias)), int(filter_radius),
+                            float(normal_min))
+        st = stats if stats is not None else _abi.rg_stats()
+        _abi.check(_abi.lib().rg_render_image_ambient(
+            self.handle, width, height, C.byref(m), out.ctypes.data, rgb.ctypes.data if rgb is not None else None,
+            aof.ctypes.data if aof is not None else None, C.byref(st)), "rg_render_image_ambient")
+        res = (out,) + ((rgb,) if want_rgb else ()) + ((aof,) if want_ao else ())
+        return res if len(res) > 1 else out
+
     def trace(self, rays: np.ndarray):
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         n = rays.shape[0]
@@ -691,6 +730,19 @@ class Scene:                   # scene.rs:11-31
         try:
             ds.set_camera(camera)
             return ds.render_ao(width, height, samples, radius, bias)
+        finally:
+            ds.close()
+
+    # render_image's frame plus an ambient light weighted by the filtered AO pass (rg_render_image_ambient;
+    # raingun_amd/ambient.py): the (H, W, 4) uint8 frame
+    def render_ambient(self, width: int, height: int, color, ao_samples: int, ao_radius: float = float("inf"),
+                       ao_bias: float = 1e-13, samples: int = 1, filter_radius: int = 2, normal_min: float = 0.9,
+                       device: int = 0, camera: Optional[Camera] = None) -> np.ndarray:
+        ds = DeviceScene(self, device)
+        try:
+            ds.set_camera(camera)
+            return ds.render_ambient(width, height, color, ao_samples, ao_radius, ao_bias, samples, filter_radius,
+                                     normal_min)
         finally:
             ds.close()
 
