@@ -42,7 +42,6 @@ void rg_aa_res_release(rg_aa_res &r) {
     if (r.d_list) (void)hipFree(r.d_list);
     if (r.d_counts) (void)hipFree(r.d_counts);
     if (r.h_counts) (void)hipHostFree(r.h_counts);
-    if (r.d_lens) (void)hipFree(r.d_lens);
     for (int i = 0; i < 2; ++i) {
         if (r.slot_rgba[i]) (void)hipFree(r.slot_rgba[i]);
         if (r.slot_rgb[i]) (void)hipFree(r.slot_rgb[i]);
@@ -89,16 +88,7 @@ rg_status ensure_aa_res(const rg_scene *s, const aa_plan &p) {
     if ((rg_lens_active(s->lens.aperture, p.k) || rg_area_active(s->area_any, p.k)) && !r.d_lens) {
         double table[RG_LENS_TABLE_DOUBLES];
         rg_lens_make_tables(table);
-        void *d = nullptr;
-        if (!ok(hipMalloc(&d, sizeof table))) {
-            (void)hipGetLastError();
-            return RG_ERR_OUT_OF_MEMORY;
-        }
-        if (!ok(hipMemcpy(d, table, sizeof table, hipMemcpyHostToDevice))) {
-            (void)hipFree(d);
-            return RG_ERR_DEVICE;
-        }
-        r.d_lens = static_cast<double *>(d);
+        if ((st = rg_table_once(s, r.d_lens, table, sizeof table)) != RG_OK) return st;
     }
     // a replica's area table, which rg_scene_set_light_radii of the scene it copies did not write
     if (rg_area_active(s->area_any, p.k) && (s->area_stale || !s->d_area)) {
@@ -297,20 +287,19 @@ void adaptive_pass_times(rg_aa_res &r) {
 
 // Rays of the base frame plus the bands'.  A device error: the lower of the base pass's failing
 // pixel and the output pixel that contains the lowest-index failing traced sample (aa_stats'
-// mapping), with that pixel's status; on a tie the base pass's.
+// mapping), with that pixel's status; on a tie the base pass's, which is folded first.
 rg_status adaptive_stats(const rg_scene *s, const aa_plan &p, rg_stats *stats) {
     rg_aa_res &r = s->aa;
-    rg_stats total, base;
+    rg_stats bands, base;
     adaptive_pass_times(r);
-    rg_status err = aa_stats(s, p, &total);
-    const rg_status err0 = rg_snap_status(r.h_snap + 4 * (size_t)p.bands, &base);
-    total.rays.primary += base.rays.primary;
-    total.rays.shadow += base.rays.shadow;
-    total.rays.secondary += base.rays.secondary;
-    if (err0 != RG_OK && (err == RG_OK || base.error_pixel <= total.error_pixel)) {
-        err = err0;
-        total.error_pixel = base.error_pixel;
-    }
+    const rg_status err_bands = aa_stats(s, p, &bands);
+    const rg_status err_base = rg_snap_status(r.h_snap + 4 * (size_t)p.bands, &base);
+    rg_stats total{};
+    total.kernel_ms = bands.kernel_ms;
+    total.error_pixel = -1;
+    rg_status err = RG_OK;
+    rg_stats_add(total, err, base, err_base);
+    rg_stats_add(total, err, bands, err_bands);
     if (stats) *stats = total;
     return err;
 }
@@ -392,28 +381,21 @@ rg_status rg_edge_mask(int32_t device, const uint8_t *rgba_in, uint32_t width, u
         return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(device))) return RG_ERR_DEVICE;
     const size_t px = (size_t)width * height;
-    void *d_in = nullptr, *d_mask = nullptr, *d_n = nullptr;
     const size_t n_bytes = (size_t)RG_EDGE_SHARDS * RG_EDGE_SHARD_WORDS * 4;
     std::vector<uint32_t> shard(n_bytes / 4);
+    rg_scratch mem;
+    uint8_t *d_in = mem.dev<uint8_t>(px * 4), *d_mask = mem.dev<uint8_t>(px + 16);
+    uint32_t *d_n = mem.dev<uint32_t>(n_bytes);
+    if (mem.status() != RG_OK) return mem.status();
+    if (!ok(hipMemcpy(d_in, rgba_in, px * 4, hipMemcpyHostToDevice)) || !ok(hipMemset(d_n, 0, n_bytes)) ||
+        !ok(rg_launch_edge_mask(d_in, width, height, threshold, d_mask, d_n, nullptr)) ||
+        !ok(hipMemcpy(mask_out, d_mask, px, hipMemcpyDeviceToHost)) ||
+        !ok(hipMemcpy(shard.data(), d_n, n_bytes, hipMemcpyDeviceToHost)))
+        return RG_ERR_DEVICE;
     uint32_t n = 0;
-    rg_status st = RG_OK;
-    if (!ok(hipMalloc(&d_in, px * 4)) || !ok(hipMalloc(&d_mask, px + 16)) || !ok(hipMalloc(&d_n, n_bytes))) {
-        (void)hipGetLastError();
-        st = RG_ERR_OUT_OF_MEMORY;
-    }
-    if (st == RG_OK &&
-        (!ok(hipMemcpy(d_in, rgba_in, px * 4, hipMemcpyHostToDevice)) || !ok(hipMemset(d_n, 0, n_bytes)) ||
-         !ok(rg_launch_edge_mask(static_cast<const uint8_t *>(d_in), width, height, threshold,
-                                 static_cast<uint8_t *>(d_mask), static_cast<uint32_t *>(d_n), nullptr)) ||
-         !ok(hipMemcpy(mask_out, d_mask, px, hipMemcpyDeviceToHost)) ||
-         !ok(hipMemcpy(shard.data(), d_n, n_bytes, hipMemcpyDeviceToHost))))
-        st = RG_ERR_DEVICE;
     for (size_t i = 0; i < RG_EDGE_SHARDS; ++i) n += shard[i * RG_EDGE_SHARD_WORDS];
-    if (d_in) (void)hipFree(d_in);
-    if (d_mask) (void)hipFree(d_mask);
-    if (d_n) (void)hipFree(d_n);
-    if (st == RG_OK && flagged) *flagged = n;
-    return st;
+    if (flagged) *flagged = n;
+    return RG_OK;
 }
 
 rg_status rg_render_image_aa(const rg_scene *s, uint32_t width, uint32_t height, uint32_t samples, uint8_t *rgba_out,
@@ -460,23 +442,17 @@ rg_status rg_resolve_box(int32_t device, const float *rgb_in, uint32_t width, ui
         return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(device))) return RG_ERR_DEVICE;
     const size_t in_bytes = (size_t)samples * width * samples * height * 12, px = (size_t)width * height;
-    void *d_in = nullptr, *d_rgba = nullptr, *d_rgb = nullptr;
-    rg_status st = RG_OK;
-    if (!ok(hipMalloc(&d_in, in_bytes)) || !ok(hipMalloc(&d_rgba, px * 4)) || (rgb_out && !ok(hipMalloc(&d_rgb, px * 12)))) {
-        (void)hipGetLastError();
-        st = RG_ERR_OUT_OF_MEMORY;
-    }
-    if (st == RG_OK &&
-        (!ok(hipMemcpy(d_in, rgb_in, in_bytes, hipMemcpyHostToDevice)) ||
-         !ok(rg_launch_resolve(static_cast<const float *>(d_in), width, height, samples, static_cast<uint8_t *>(d_rgba),
-                               static_cast<float *>(d_rgb), nullptr)) ||
-         !ok(hipMemcpy(rgba_out, d_rgba, px * 4, hipMemcpyDeviceToHost)) ||
-         (rgb_out && !ok(hipMemcpy(rgb_out, d_rgb, px * 12, hipMemcpyDeviceToHost)))))
-        st = RG_ERR_DEVICE;
-    if (d_in) (void)hipFree(d_in);
-    if (d_rgba) (void)hipFree(d_rgba);
-    if (d_rgb) (void)hipFree(d_rgb);
-    return st;
+    rg_scratch mem;
+    float *d_in = mem.dev<float>(in_bytes);
+    uint8_t *d_rgba = mem.dev<uint8_t>(px * 4);
+    float *d_rgb = rgb_out ? mem.dev<float>(px * 12) : nullptr;
+    if (mem.status() != RG_OK) return mem.status();
+    if (!ok(hipMemcpy(d_in, rgb_in, in_bytes, hipMemcpyHostToDevice)) ||
+        !ok(rg_launch_resolve(d_in, width, height, samples, d_rgba, d_rgb, nullptr)) ||
+        !ok(hipMemcpy(rgba_out, d_rgba, px * 4, hipMemcpyDeviceToHost)) ||
+        (rgb_out && !ok(hipMemcpy(rgb_out, d_rgb, px * 12, hipMemcpyDeviceToHost))))
+        return RG_ERR_DEVICE;
+    return RG_OK;
 }
 
 rg_status rg_debug_set_aa_adaptive_timing(rg_scene *s, int32_t enable) {

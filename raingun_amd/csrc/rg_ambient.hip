@@ -24,11 +24,6 @@ bool filter_args_ok(const void *ao, const void *body, const void *normal, uint32
            (unsigned long long)W * H < (1ull << 32) && rg_ao_filter_valid(f->radius, f->normal_min);
 }
 
-// A device error that still delivers its frame: the reference's panics.
-bool is_panic(rg_status st) {
-    return st == RG_ERR_AABB_NORMAL || st == RG_ERR_NAN_DISTANCE || st == RG_ERR_TRANSMISSION;
-}
-
 rg_status ambient_check(const rg_scene *s, uint32_t W, uint32_t H, const rg_ambient *m, const void *rgba) {
     if (!s || !m || !rgba || W == 0 || H == 0) return RG_ERR_INVALID_ARGUMENT;
     if (!rg_ambient_valid(m->color, m->samples, m->filter_radius, m->normal_min) ||
@@ -42,22 +37,10 @@ rg_status ambient_check(const rg_scene *s, uint32_t W, uint32_t H, const rg_ambi
 
 bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
-// The scene's share table on its device: made on the first ambient frame, never rewritten.
+// The scene's share table on its device, made on the first ambient frame (no body: one float, nothing copied).
 rg_status share_table(const rg_scene *s) {
-    if (s->d_share) return RG_OK;
     const std::vector<float> &h = s->host->amb_share;
-    const size_t bytes = (h.empty() ? 1 : h.size()) * sizeof(float);
-    void *d = nullptr;
-    if (!ok(hipMalloc(&d, bytes))) {
-        (void)hipGetLastError();
-        return RG_ERR_OUT_OF_MEMORY;
-    }
-    if (!h.empty() && !ok(hipMemcpy(d, h.data(), bytes, hipMemcpyHostToDevice))) {
-        (void)hipFree(d);
-        return RG_ERR_DEVICE;
-    }
-    s->d_share = static_cast<float *>(d);
-    return RG_OK;
+    return rg_table_once(s, s->d_share, h.empty() ? nullptr : h.data(), (h.empty() ? 1 : h.size()) * sizeof(float));
 }
 
 // The stream's resource set with at least `bytes` of scratch (nullptr: out of memory / device error).  A set is
@@ -116,27 +99,18 @@ rg_status rg_ao_filter(int32_t device, const float *ao_in, const int32_t *body, 
     if (device < 0 || !filter_args_ok(ao_in, body, normal, width, height, filter, ao_out)) return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(device))) return RG_ERR_DEVICE;
     const size_t px = (size_t)width * height;
-    void *d_ao = nullptr, *d_body = nullptr, *d_n = nullptr, *d_out = nullptr;
-    rg_status st = RG_OK;
-    if (!ok(hipMalloc(&d_ao, px * 4)) || !ok(hipMalloc(&d_body, px * 4)) || !ok(hipMalloc(&d_n, px * 12)) ||
-        !ok(hipMalloc(&d_out, px * 4))) {
-        (void)hipGetLastError();
-        st = RG_ERR_OUT_OF_MEMORY;
-    }
-    if (st == RG_OK &&
-        (!ok(hipMemcpy(d_ao, ao_in, px * 4, hipMemcpyHostToDevice)) ||
-         !ok(hipMemcpy(d_body, body, px * 4, hipMemcpyHostToDevice)) ||
-         !ok(hipMemcpy(d_n, normal, px * 12, hipMemcpyHostToDevice)) ||
-         !ok(rg_launch_ao_filter(static_cast<const float *>(d_ao), static_cast<const int32_t *>(d_body),
-                                 static_cast<const float *>(d_n), width, height, filter->radius, filter->normal_min,
-                                 static_cast<float *>(d_out), nullptr)) ||
-         !ok(hipMemcpy(ao_out, d_out, px * 4, hipMemcpyDeviceToHost))))
-        st = RG_ERR_DEVICE;
-    if (d_ao) (void)hipFree(d_ao);
-    if (d_body) (void)hipFree(d_body);
-    if (d_n) (void)hipFree(d_n);
-    if (d_out) (void)hipFree(d_out);
-    return st;
+    rg_scratch mem;
+    float *d_ao = mem.dev<float>(px * 4);
+    int32_t *d_body = mem.dev<int32_t>(px * 4);
+    float *d_n = mem.dev<float>(px * 12), *d_out = mem.dev<float>(px * 4);
+    if (mem.status() != RG_OK) return mem.status();
+    if (!ok(hipMemcpy(d_ao, ao_in, px * 4, hipMemcpyHostToDevice)) ||
+        !ok(hipMemcpy(d_body, body, px * 4, hipMemcpyHostToDevice)) ||
+        !ok(hipMemcpy(d_n, normal, px * 12, hipMemcpyHostToDevice)) ||
+        !ok(rg_launch_ao_filter(d_ao, d_body, d_n, width, height, filter->radius, filter->normal_min, d_out, nullptr)) ||
+        !ok(hipMemcpy(ao_out, d_out, px * 4, hipMemcpyDeviceToHost)))
+        return RG_ERR_DEVICE;
+    return RG_OK;
 }
 
 rg_status rg_render_ambient_async(const rg_scene *s, uint32_t width, uint32_t height, const rg_ambient *m,
@@ -169,11 +143,11 @@ rg_status rg_render_ambient_async(const rg_scene *s, uint32_t width, uint32_t he
     const rg_aov layers = {body, nullptr, normal, nullptr, albedo};
     rg_status pst[3];
     pst[0] = rg_render_aa_async(s, width, height, m->samples, rgba_dev, rgb, stream, stats ? &pass[0] : nullptr);
-    if (pst[0] != RG_OK && !is_panic(pst[0])) return pst[0];
+    if (!rg_delivers_frame(pst[0])) return pst[0];
     pst[1] = rg_render_aov_async(s, width, height, &whole, &layers, stream, stats ? &pass[1] : nullptr);
-    if (pst[1] != RG_OK && !is_panic(pst[1])) return pst[1];
+    if (!rg_delivers_frame(pst[1])) return pst[1];
     pst[2] = rg_render_ao_async(s, width, height, &whole, &m->ao, raw, stream, stats ? &pass[2] : nullptr);
-    if (pst[2] != RG_OK && !is_panic(pst[2])) return pst[2];
+    if (!rg_delivers_frame(pst[2])) return pst[2];
 
     if (stats && !ok(hipEventRecord(r->ev0, hs))) return RG_ERR_DEVICE;
     if (filtered && !ok(rg_launch_ao_filter(raw, body, normal, width, height, m->filter_radius, m->normal_min, aof, hs)))
@@ -185,22 +159,11 @@ rg_status rg_render_ambient_async(const rg_scene *s, uint32_t width, uint32_t he
     if (!ok(hipEventRecord(r->ev1, hs)) || !ok(hipStreamSynchronize(hs))) return RG_ERR_DEVICE;
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, r->ev0, r->ev1);
-    rg_stats total = pass[0];
+    rg_stats total{};
     total.kernel_ms = pass[0].kernel_ms + pass[1].kernel_ms + pass[2].kernel_ms + ms;
     total.error_pixel = -1;
     st = RG_OK;
-    for (int i = 0; i < 3; ++i) {
-        if (i > 0) {
-            total.rays.primary += pass[i].rays.primary;
-            total.rays.shadow += pass[i].rays.shadow;
-            total.rays.secondary += pass[i].rays.secondary;
-        }
-        // the lowest failing pixel; a tie keeps the earlier pass's
-        if (pst[i] != RG_OK && (st == RG_OK || pass[i].error_pixel < total.error_pixel)) {
-            st = pst[i];
-            total.error_pixel = pass[i].error_pixel;
-        }
-    }
+    for (int i = 0; i < 3; ++i) rg_stats_add(total, st, pass[i], pst[i]);  // a tie keeps the earlier pass's
     *stats = total;
     return st;
 }
@@ -211,25 +174,19 @@ rg_status rg_render_image_ambient(const rg_scene *s, uint32_t width, uint32_t he
     if (st != RG_OK) return st;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
     const size_t px = (size_t)width * height;
-    void *d_rgba = nullptr, *d_rgb = nullptr, *d_ao = nullptr;
-    if (!ok(hipMalloc(&d_rgba, px * 4)) || (rgb_out && !ok(hipMalloc(&d_rgb, px * 12))) ||
-        (ao_out && !ok(hipMalloc(&d_ao, px * 4)))) {
-        (void)hipGetLastError();
-        st = RG_ERR_OUT_OF_MEMORY;
-    }
+    rg_scratch mem;
+    uint8_t *d_rgba = mem.dev<uint8_t>(px * 4);
+    float *d_rgb = rgb_out ? mem.dev<float>(px * 12) : nullptr;
+    float *d_ao = ao_out ? mem.dev<float>(px * 4) : nullptr;
+    if (mem.status() != RG_OK) return mem.status();
     rg_stats local;
-    if (st == RG_OK)
-        st = rg_render_ambient_async(s, width, height, m, static_cast<uint8_t *>(d_rgba), static_cast<float *>(d_rgb),
-                                     static_cast<float *>(d_ao), nullptr, stats ? stats : &local);
+    st = rg_render_ambient_async(s, width, height, m, d_rgba, d_rgb, d_ao, nullptr, stats ? stats : &local);
     // the frame is delivered on the reference's panics too
-    if ((st == RG_OK || is_panic(st)) &&
+    if (rg_delivers_frame(st) &&
         (!ok(hipMemcpy(rgba_out, d_rgba, px * 4, hipMemcpyDeviceToHost)) ||
          (rgb_out && !ok(hipMemcpy(rgb_out, d_rgb, px * 12, hipMemcpyDeviceToHost))) ||
          (ao_out && !ok(hipMemcpy(ao_out, d_ao, px * 4, hipMemcpyDeviceToHost)))))
         st = RG_ERR_DEVICE;
-    if (d_rgba) (void)hipFree(d_rgba);
-    if (d_rgb) (void)hipFree(d_rgb);
-    if (d_ao) (void)hipFree(d_ao);
     return st;
 }
 

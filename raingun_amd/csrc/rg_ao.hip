@@ -51,16 +51,10 @@ hipError_t launch_flavour(const RgKernelArgs *a, const RgAoArgs *o, dim3 grid, s
 extern "C" hipError_t rg_launch_ao(const RgKernelArgs *a, const RgAoArgs *o, hipStream_t stream) {
     if (a->out_rows == 0 || a->width == 0 || a->tile_wlog < 3 || a->tile_wlog > 6) return hipErrorInvalidValue;
     if (!o->out || !o->tab || !rg_ao_valid(o->samples, o->radius, o->bias)) return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    dim3 grid;
+    size_t lds = 0;
+    const hipError_t e = rg_pass_grid(*a, RG_AO_BLOCK, RG_AO_BLOCKS_PER_CU, &grid, &lds);
     if (e != hipSuccess) return e;
-    const unsigned long long ntiles = rg_tile_count(*a), per_block = RG_AO_BLOCK / 64u;
-    const unsigned long long want = (ntiles + per_block - 1ull) / per_block;
-    const unsigned long long cap = (unsigned long long)(cus > 0 ? cus : 1) * RG_AO_BLOCKS_PER_CU;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
-    // per-lane walk stacks (stride = block size): lane_stack entries + the spare slot (rg_k_bvh.h bvh_lane)
-    const size_t lds = a->lane_stack > 0 ? ((size_t)(a->lane_stack + 1) * 4u) * RG_AO_BLOCK : 0u;
     return a->camera ? launch_flavour<true>(a, o, grid, lds, stream) : launch_flavour<false>(a, o, grid, lds, stream);
 }
 
@@ -69,53 +63,16 @@ namespace {
 
 bool ao_ok(const rg_ao *ao) { return ao && rg_ao_valid(ao->samples, ao->radius, ao->bias); }
 
-// The scene's arguments plus this launch's frame, tiling, camera and counter sets (what
-// rg_launch_tiles sets of them; the kernel reads nothing else).
-RgKernelArgs ao_args(const rg_scene *s, rg_launch_ctx *cx, uint32_t W, uint32_t H, const rg_tiling &t, uint32_t rows) {
-    RgKernelArgs a = rg_make_args(s);
-    a.counters = cx->counters + (size_t)cx->cur * RG_COUNTER_WORDS;  // zero (rg_launch_ctx::counters)
-    a.counters_next = cx->counters + (size_t)(1 - cx->cur) * RG_COUNTER_WORDS;
-    a.err_sticky = cx->sticky;
-    a.width = W;
-    a.height = H;
-    a.tile_rows = t.tile_rows;
-    a.tile_stride = t.tile_stride;
-    a.tile_offset = t.tile_offset;
-    a.tile_group = 1u;
-    a.out_rows = rows;
-    a.width_d = (double)W;
-    a.height_d = (double)H;
-    a.aspect = a.width_d / a.height_d;
-    a.tile_wlog = RG_AO_TILE_WLOG;
-    if (s->has_camera) {  // by value: this launch keeps its camera whatever the scene is given next
-        a.camera = 1u;
-        for (int k = 0; k < 3; ++k) {
-            a.cam_eye[k] = s->camera.eye[k];
-            a.cam_right[k] = s->camera.right[k];
-            a.cam_up[k] = s->camera.up[k];
-            a.cam_forward[k] = s->camera.forward[k];
-        }
-    }
-    return a;
+hipError_t launch_pass(const RgKernelArgs *a, const void *o, hipStream_t stream) {
+    return rg_launch_ao(a, static_cast<const RgAoArgs *>(o), stream);
 }
 
-// The scene's AO table on its device: made on the first AO frame, never rewritten, so launches in flight may
-// read it whatever comes next.
+// The scene's AO table on its device, made on the first AO frame.
 rg_status ao_table(const rg_scene *s) {
     if (s->d_ao) return RG_OK;
     double table[RG_AO_TABLE_DOUBLES];
     rg_ao_make_table(table);
-    void *d = nullptr;
-    if (!ok(hipMalloc(&d, sizeof table))) {
-        (void)hipGetLastError();
-        return RG_ERR_OUT_OF_MEMORY;
-    }
-    if (!ok(hipMemcpy(d, table, sizeof table, hipMemcpyHostToDevice))) {
-        (void)hipFree(d);
-        return RG_ERR_DEVICE;
-    }
-    s->d_ao = static_cast<double *>(d);
-    return RG_OK;
+    return rg_table_once(s, s->d_ao, table, sizeof table);
 }
 
 }  // namespace
@@ -130,38 +87,13 @@ rg_status rg_ao_tables(uint32_t samples, double *points) {
 
 rg_status rg_render_ao_async(const rg_scene *s, uint32_t width, uint32_t height, const rg_tiling *tiling, const rg_ao *ao,
                              float *ao_dev, void *stream, rg_stats *stats) {
-    if (!s || !ao_ok(ao) || !ao_dev || width == 0 || height == 0 || !tiling || !rg_tiling_valid(tiling))
-        return RG_ERR_INVALID_ARGUMENT;
-    if (width < height) return RG_ERR_PORTRAIT;  // ray.rs:42
-    const uint32_t rows = rg_tiling_rows(height, tiling);
-    if ((unsigned long long)rows * width >= (1ull << 32) || (unsigned long long)height * width >= (1ull << 32))
-        return RG_ERR_INVALID_ARGUMENT;  // the reference's u32 pixel index (rendering.rs:27)
-    if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
-    rg_status st = ao_table(s);
-    if (st != RG_OK) return st;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    rg_launch_ctx *cx = rg_ctx_for(s, hs);
-    if (!cx) return RG_ERR_OUT_OF_MEMORY;
-    s->last = cx;
-    RgKernelArgs a = ao_args(s, cx, width, height, *tiling, rows);
+    if (!s || !ao_ok(ao) || !ao_dev) return RG_ERR_INVALID_ARGUMENT;
+    uint32_t rows = 0;
+    rg_status st = rg_pass_check(s, width, height, tiling, &rows);
+    if (st != RG_OK || (st = ao_table(s)) != RG_OK) return st;
     const RgAoArgs o{ao_dev, s->d_ao, ao->samples, 0u, ao->radius, ao->bias};
-    cx->last_counters = a.counters;
-    cx->last_plain = 0;
-    cx->last_shvol = 0;
-    if (stats && !ok(hipEventRecord(cx->ev0, hs))) return RG_ERR_DEVICE;
-    if (rows > 0) {
-        if (!ok(rg_launch_ao(&a, &o, hs))) return RG_ERR_DEVICE;
-        cx->cur = 1 - cx->cur;  // the kernel zeroes the other set for the next launch
-    }
-    if (!stats) return RG_OK;
-    unsigned long long c[4];
-    if (!ok(hipEventRecord(cx->ev1, hs)) ||
-        !ok(hipMemcpyAsync(c, a.counters, sizeof c, hipMemcpyDeviceToHost, hs)) || !ok(hipStreamSynchronize(hs)))
-        return RG_ERR_DEVICE;
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, cx->ev0, cx->ev1);
-    stats->kernel_ms = ms;
-    return rg_snap_status(c, stats);
+    return rg_pass_enqueue(s, width, height, *tiling, rows, static_cast<hipStream_t>(stream), RG_AO_TILE_WLOG, stats,
+                           launch_pass, &o);
 }
 
 rg_status rg_render_ao(const rg_scene *s, uint32_t width, uint32_t height, const rg_ao *ao, float *ao_out,
@@ -171,19 +103,15 @@ rg_status rg_render_ao(const rg_scene *s, uint32_t width, uint32_t height, const
     const unsigned long long npx = (unsigned long long)width * height;
     if (npx >= (1ull << 32)) return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
-    void *d = nullptr;
-    if (!ok(hipMalloc(&d, (size_t)npx * sizeof(float)))) {
-        (void)hipGetLastError();
-        return RG_ERR_OUT_OF_MEMORY;
-    }
+    rg_scratch mem;
+    float *d = mem.dev<float>((size_t)npx * sizeof(float));
+    if (mem.status() != RG_OK) return mem.status();
     const rg_tiling whole = {height, 1, 0};
     rg_stats local;
-    rg_status st = rg_render_ao_async(s, width, height, &whole, ao, static_cast<float *>(d), nullptr, stats ? stats : &local);
+    rg_status st = rg_render_ao_async(s, width, height, &whole, ao, d, nullptr, stats ? stats : &local);
     // the frame is delivered on the reference's panics too
-    if ((st == RG_OK || st == RG_ERR_AABB_NORMAL || st == RG_ERR_NAN_DISTANCE) &&
-        !ok(hipMemcpy(ao_out, d, (size_t)npx * sizeof(float), hipMemcpyDeviceToHost)))
+    if (rg_delivers_frame(st) && !ok(hipMemcpy(ao_out, d, (size_t)npx * sizeof(float), hipMemcpyDeviceToHost)))
         st = RG_ERR_DEVICE;
-    (void)hipFree(d);
     return st;
 }
 

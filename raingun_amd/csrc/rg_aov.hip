@@ -57,16 +57,10 @@ hipError_t launch_flavour(const RgKernelArgs *a, const RgAovOut *o, dim3 grid, s
 
 extern "C" hipError_t rg_launch_aov(const RgKernelArgs *a, const RgAovOut *o, hipStream_t stream) {
     if (a->out_rows == 0 || a->width == 0 || a->tile_wlog < 3 || a->tile_wlog > 6) return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    dim3 grid;
+    size_t lds = 0;
+    const hipError_t e = rg_pass_grid(*a, RG_AOV_BLOCK, RG_AOV_BLOCKS_PER_CU, &grid, &lds);
     if (e != hipSuccess) return e;
-    const unsigned long long ntiles = rg_tile_count(*a), per_block = RG_AOV_BLOCK / 64u;
-    const unsigned long long want = (ntiles + per_block - 1ull) / per_block;
-    const unsigned long long cap = (unsigned long long)(cus > 0 ? cus : 1) * RG_AOV_BLOCKS_PER_CU;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
-    // per-lane walk stacks (stride = block size): lane_stack entries + the spare slot (rg_k_bvh.h bvh_lane)
-    const size_t lds = a->lane_stack > 0 ? ((size_t)(a->lane_stack + 1) * 4u) * RG_AOV_BLOCK : 0u;
     return a->camera ? launch_flavour<true>(a, o, grid, lds, stream) : launch_flavour<false>(a, o, grid, lds, stream);
 }
 
@@ -75,34 +69,8 @@ namespace {
 
 bool any_layer(const rg_aov *v) { return v->body || v->depth || v->normal || v->uv || v->albedo; }
 
-// The scene's arguments plus this launch's frame, tiling, camera and counter sets (what
-// rg_launch_tiles sets of them; the kernel reads nothing else).
-RgKernelArgs aov_args(const rg_scene *s, rg_launch_ctx *cx, uint32_t W, uint32_t H, const rg_tiling &t, uint32_t rows) {
-    RgKernelArgs a = rg_make_args(s);
-    a.counters = cx->counters + (size_t)cx->cur * RG_COUNTER_WORDS;  // zero (rg_launch_ctx::counters)
-    a.counters_next = cx->counters + (size_t)(1 - cx->cur) * RG_COUNTER_WORDS;
-    a.err_sticky = cx->sticky;
-    a.width = W;
-    a.height = H;
-    a.tile_rows = t.tile_rows;
-    a.tile_stride = t.tile_stride;
-    a.tile_offset = t.tile_offset;
-    a.tile_group = 1u;
-    a.out_rows = rows;
-    a.width_d = (double)W;
-    a.height_d = (double)H;
-    a.aspect = a.width_d / a.height_d;
-    a.tile_wlog = RG_AOV_TILE_WLOG;
-    if (s->has_camera) {  // by value: this launch keeps its camera whatever the scene is given next
-        a.camera = 1u;
-        for (int k = 0; k < 3; ++k) {
-            a.cam_eye[k] = s->camera.eye[k];
-            a.cam_right[k] = s->camera.right[k];
-            a.cam_up[k] = s->camera.up[k];
-            a.cam_forward[k] = s->camera.forward[k];
-        }
-    }
-    return a;
+hipError_t launch_pass(const RgKernelArgs *a, const void *o, hipStream_t stream) {
+    return rg_launch_aov(a, static_cast<const RgAovOut *>(o), stream);
 }
 
 }  // namespace
@@ -111,36 +79,13 @@ extern "C" {
 
 rg_status rg_render_aov_async(const rg_scene *s, uint32_t width, uint32_t height, const rg_tiling *tiling,
                               const rg_aov *dev, void *stream, rg_stats *stats) {
-    if (!s || !dev || !any_layer(dev) || width == 0 || height == 0 || !tiling || !rg_tiling_valid(tiling))
-        return RG_ERR_INVALID_ARGUMENT;
-    if (width < height) return RG_ERR_PORTRAIT;  // ray.rs:42
-    const uint32_t rows = rg_tiling_rows(height, tiling);
-    if ((unsigned long long)rows * width >= (1ull << 32) || (unsigned long long)height * width >= (1ull << 32))
-        return RG_ERR_INVALID_ARGUMENT;  // the reference's u32 pixel index (rendering.rs:27)
-    if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rg_launch_ctx *cx = rg_ctx_for(s, st);
-    if (!cx) return RG_ERR_OUT_OF_MEMORY;
-    s->last = cx;
-    RgKernelArgs a = aov_args(s, cx, width, height, *tiling, rows);
+    if (!s || !dev || !any_layer(dev)) return RG_ERR_INVALID_ARGUMENT;
+    uint32_t rows = 0;
+    const rg_status st = rg_pass_check(s, width, height, tiling, &rows);
+    if (st != RG_OK) return st;
     const RgAovOut o{dev->body, dev->depth, dev->normal, dev->uv, dev->albedo};
-    cx->last_counters = a.counters;
-    cx->last_plain = 0;
-    cx->last_shvol = 0;
-    if (stats && !ok(hipEventRecord(cx->ev0, st))) return RG_ERR_DEVICE;
-    if (rows > 0) {
-        if (!ok(rg_launch_aov(&a, &o, st))) return RG_ERR_DEVICE;
-        cx->cur = 1 - cx->cur;  // the kernel zeroes the other set for the next launch
-    }
-    if (!stats) return RG_OK;
-    unsigned long long c[4];
-    if (!ok(hipEventRecord(cx->ev1, st)) ||
-        !ok(hipMemcpyAsync(c, a.counters, sizeof c, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
-        return RG_ERR_DEVICE;
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, cx->ev0, cx->ev1);
-    stats->kernel_ms = ms;
-    return rg_snap_status(c, stats);
+    return rg_pass_enqueue(s, width, height, *tiling, rows, static_cast<hipStream_t>(stream), RG_AOV_TILE_WLOG, stats,
+                           launch_pass, &o);
 }
 
 rg_status rg_render_aov(const rg_scene *s, uint32_t width, uint32_t height, const rg_aov *out, rg_stats *stats) {
@@ -152,27 +97,19 @@ rg_status rg_render_aov(const rg_scene *s, uint32_t width, uint32_t height, cons
     // the requested layers in device memory, one plain copy each after the launch
     void *const host[5] = {out->body, out->depth, out->normal, out->uv, out->albedo};
     const size_t px_bytes[5] = {4, 8, 12, 8, 12};
-    void *d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    rg_status st = RG_OK;
-    for (int k = 0; k < 5 && st == RG_OK; ++k)
-        if (host[k] && !ok(hipMalloc(&d[k], (size_t)npx * px_bytes[k]))) {
-            (void)hipGetLastError();
-            st = RG_ERR_OUT_OF_MEMORY;
-        }
-    if (st == RG_OK) {
-        const rg_aov dev{static_cast<int32_t *>(d[0]), static_cast<double *>(d[1]), static_cast<float *>(d[2]),
-                         static_cast<float *>(d[3]), static_cast<float *>(d[4])};
-        const rg_tiling whole = {height, 1, 0};
-        rg_stats local;
-        st = rg_render_aov_async(s, width, height, &whole, &dev, nullptr, stats ? stats : &local);
-        // the frame is delivered on the reference's panics too
-        if (st == RG_OK || st == RG_ERR_AABB_NORMAL || st == RG_ERR_NAN_DISTANCE)
-            for (int k = 0; k < 5; ++k)
-                if (host[k] && !ok(hipMemcpy(host[k], d[k], (size_t)npx * px_bytes[k], hipMemcpyDeviceToHost)))
-                    st = RG_ERR_DEVICE;
-    }
-    for (int k = 0; k < 5; ++k)
-        if (d[k]) (void)hipFree(d[k]);
+    rg_scratch mem;
+    void *d[5];
+    for (int k = 0; k < 5; ++k) d[k] = host[k] ? mem.dev<void>((size_t)npx * px_bytes[k]) : nullptr;
+    if (mem.status() != RG_OK) return mem.status();
+    const rg_aov dev{static_cast<int32_t *>(d[0]), static_cast<double *>(d[1]), static_cast<float *>(d[2]),
+                     static_cast<float *>(d[3]), static_cast<float *>(d[4])};
+    const rg_tiling whole = {height, 1, 0};
+    rg_stats local;
+    rg_status st = rg_render_aov_async(s, width, height, &whole, &dev, nullptr, stats ? stats : &local);
+    const bool deliver = rg_delivers_frame(st);  // on the reference's panics too
+    for (int k = 0; k < 5 && deliver; ++k)
+        if (host[k] && !ok(hipMemcpy(host[k], d[k], (size_t)npx * px_bytes[k], hipMemcpyDeviceToHost)))
+            st = RG_ERR_DEVICE;
     return st;
 }
 

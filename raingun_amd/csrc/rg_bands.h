@@ -59,9 +59,9 @@ bool rg_bands_join(rg_band_res &r);
 rg_status rg_bands_deliver(rg_band_res &r, const rg_band_plan &p, const uint8_t *d_rgba, const float *d_rgb,
                            uint8_t *rgba_out, float *rgb_out);
 
-// Ray counts summed over n band snapshots (4 words each), the first erroring snapshot's status
-// and pixel (bands in row order: the lowest erroring pixel), kernel_ms = ev_t0 .. ev_t1, into
-// `stats` (nullable).
+// Ray counts summed over n band snapshots (4 words each), the status and pixel of the lowest
+// erroring pixel (rg_stats_merge.h; bands come in row order, so it is the first erroring
+// snapshot's), kernel_ms = ev_t0 .. ev_t1, into `stats` (nullable).
 rg_status rg_finish_stats(const unsigned long long *snap, int n, hipEvent_t ev_t0, hipEvent_t ev_t1, rg_stats *stats);
 
 #pragma GCC visibility pop

@@ -140,6 +140,7 @@ rg_status rg_bands_deliver(rg_band_res &r, const rg_band_plan &p, const uint8_t 
     return RG_OK;
 }
 
+// Bands in ascending pixel order, so "the lowest failing pixel" is the first failing band (rg_stats_merge.h).
 static rg_status rg_merge_band_snaps(const unsigned long long *snap, int n, rg_stats *total) {
     std::memset(total, 0, sizeof *total);
     total->error_pixel = -1;
@@ -147,13 +148,7 @@ static rg_status rg_merge_band_snaps(const unsigned long long *snap, int n, rg_s
     for (int b = 0; b < n; ++b) {
         rg_stats bs;
         const rg_status e = rg_snap_status(snap + 4 * b, &bs);
-        total->rays.primary += bs.rays.primary;
-        total->rays.shadow += bs.rays.shadow;
-        total->rays.secondary += bs.rays.secondary;
-        if (e != RG_OK && err == RG_OK) {
-            err = e;
-            total->error_pixel = bs.error_pixel;
-        }
+        rg_stats_add(*total, err, bs, e);
     }
     return err;
 }

@@ -10,7 +10,10 @@
 // rg_copy_pool.cpp, the single-process multi-GPU entry (rg_render_multi) in
 // rg_multi.hip (the dealing of tiles it and rg_frames.hip share in rg_tile_deal.h, their
 // pack and re-interleave kernels in rg_gather.hip, the RCCL loader in rg_rccl.hip), the
-// supersampled frames (rg_render_image_aa) in rg_aa.hip.
+// supersampled frames (rg_render_image_aa) in rg_aa.hip, the AOV pass in rg_aov.hip, the
+// ambient occlusion pass in rg_ao.hip and the ambient term in rg_ambient.hip (their shared
+// launch path, rg_pass_enqueue, in rg_launch.hip).  The blocking entries here and there keep
+// their device scratch in an rg_scratch (rg_internal.h), which frees it when they return.
 // Once a path here has enqueued work that stores into the caller's buffer,
 // every error exit drains its streams first (rg_bands_drain).  No exception or
 // abort crosses the ABI.
@@ -601,13 +604,13 @@ rg_status rg_debug_camera_check(const rg_scene *s, uint32_t width, uint32_t heig
     a.inv_h = 1.0 / a.height_d;
     if (admitted)
         *admitted = rg_recip_div_ok(width) && rg_recip_div_ok(height) && rg_camera_unscaled_ok(a.fov_adjustment, a.aspect);
-    unsigned long long *d_bad = nullptr, bad = 0;
-    if (!ok(hipMalloc(&d_bad, sizeof bad))) return RG_ERR_OUT_OF_MEMORY;
+    rg_scratch mem;
+    unsigned long long *d_bad = mem.dev<unsigned long long>(sizeof(unsigned long long)), bad = 0;
+    if (mem.status() != RG_OK) return mem.status();
     rg_status st = RG_OK;
     if (!ok(hipMemset(d_bad, 0, sizeof bad)) || !ok(rg_launch_camera_check(&a, d_bad, nullptr)) ||
         !ok(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost)))
         st = RG_ERR_DEVICE;
-    (void)hipFree(d_bad);
     *mismatches = bad;
     return st;
 }
@@ -618,23 +621,20 @@ rg_status rg_debug_unscaled_check(const rg_scene *s, int32_t op, const double *a
         return RG_ERR_INVALID_ARGUMENT;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
     const size_t bytes = (size_t)n * sizeof(double);
-    double *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
-    unsigned long long *d_bad = nullptr, bad = 0;
-    rg_status st = RG_OK;
-    if (!ok(hipMalloc(&d_a, bytes)) || (op == 2 && !ok(hipMalloc(&d_b, bytes))) || !ok(hipMalloc(&d_out, 2 * bytes)) ||
-        !ok(hipMalloc(&d_bad, sizeof bad)))
-        st = RG_ERR_OUT_OF_MEMORY;
-    else if (!ok(hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice)) ||
-             (op == 2 && !ok(hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice))) || !ok(hipMemset(d_out, 0, 2 * bytes)) ||
-             !ok(hipMemset(d_bad, 0, sizeof bad)) || !ok(rg_launch_unscaled_check(op, d_a, d_b, n, d_out, d_bad, nullptr)) ||
-             !ok(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost)))
-        st = RG_ERR_DEVICE;
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
-    (void)hipFree(d_out);
-    (void)hipFree(d_bad);
+    unsigned long long bad = 0;
+    *mismatches = 0;
+    rg_scratch mem;
+    double *d_a = mem.dev<double>(bytes), *d_b = op == 2 ? mem.dev<double>(bytes) : nullptr;
+    double *d_out = mem.dev<double>(2 * bytes);
+    unsigned long long *d_bad = mem.dev<unsigned long long>(sizeof bad);
+    if (mem.status() != RG_OK) return mem.status();
+    if (!ok(hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice)) ||
+        (op == 2 && !ok(hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice))) || !ok(hipMemset(d_out, 0, 2 * bytes)) ||
+        !ok(hipMemset(d_bad, 0, sizeof bad)) || !ok(rg_launch_unscaled_check(op, d_a, d_b, n, d_out, d_bad, nullptr)) ||
+        !ok(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost)))
+        return RG_ERR_DEVICE;
     *mismatches = bad;
-    return st;
+    return RG_OK;
 }
 
 rg_status rg_debug_counter_words(const rg_scene *s, int32_t first, int32_t n, uint64_t *out) {
@@ -650,32 +650,26 @@ rg_status rg_trace(const rg_scene *s, const double *rays, uint32_t n, double *di
     if (!s || (n && (!rays || !dist || !body))) return RG_ERR_INVALID_ARGUMENT;
     if (n == 0) return RG_OK;
     if (!ok(hipSetDevice(s->device))) return RG_ERR_DEVICE;
-    void *d_rays = nullptr, *d_dist = nullptr, *d_body = nullptr;
-    rg_status st = RG_OK;
-    if (!ok(hipMalloc(&d_rays, (size_t)n * 48)) || !ok(hipMalloc(&d_dist, (size_t)n * 8)) ||
-        !ok(hipMalloc(&d_body, (size_t)n * 4)))
-        st = RG_ERR_OUT_OF_MEMORY;
+    rg_scratch mem;
+    double *d_rays = mem.dev<double>((size_t)n * 48), *d_dist = mem.dev<double>((size_t)n * 8);
+    int32_t *d_body = mem.dev<int32_t>((size_t)n * 4);
+    if (mem.status() != RG_OK) return mem.status();
     rg_launch_ctx *cx = rg_ctx_for(s, nullptr);
-    if (!cx) st = RG_ERR_OUT_OF_MEMORY;
+    if (!cx) return RG_ERR_OUT_OF_MEMORY;
+    s->last = cx;
     RgKernelArgs a = rg_make_args(s);
-    unsigned long long c[4] = {0, 0, 0, 0};
     // the trace kernel counts into the set the context's next render launch will
     // use, and re-zeroes it after the read-back (that launch expects it zeroed)
-    unsigned long long *cs = cx ? cx->counters + (size_t)cx->cur * RG_COUNTER_WORDS : nullptr;
-    if (st == RG_OK) { s->last = cx; a.counters = cs; }
-    if (st == RG_OK && (!ok(hipMemcpy(d_rays, rays, (size_t)n * 48, hipMemcpyHostToDevice)) ||
-                        !ok(hipMemset(cs, 0, sizeof c)) ||
-                        !ok(rg_launch_trace(&a, (const double *)d_rays, n, (double *)d_dist, (int32_t *)d_body, nullptr)) ||
-                        !ok(hipMemcpy(dist, d_dist, (size_t)n * 8, hipMemcpyDeviceToHost)) ||
-                        !ok(hipMemcpy(body, d_body, (size_t)n * 4, hipMemcpyDeviceToHost)) ||
-                        !ok(hipMemcpy(c, cs, sizeof c, hipMemcpyDeviceToHost)) ||
-                        !ok(hipMemset(cs, 0, RG_COUNTER_WORDS * sizeof(unsigned long long)))))
-        st = RG_ERR_DEVICE;
-    if (d_rays) (void)hipFree(d_rays);
-    if (d_dist) (void)hipFree(d_dist);
-    if (d_body) (void)hipFree(d_body);
-    if (st == RG_OK && c[3] != 0) st = rg_snap_status(c, nullptr);
-    return st;
+    unsigned long long *cs = cx->counters + (size_t)cx->cur * RG_COUNTER_WORDS, c[4] = {0, 0, 0, 0};
+    a.counters = cs;
+    if (!ok(hipMemcpy(d_rays, rays, (size_t)n * 48, hipMemcpyHostToDevice)) || !ok(hipMemset(cs, 0, sizeof c)) ||
+        !ok(rg_launch_trace(&a, d_rays, n, d_dist, d_body, nullptr)) ||
+        !ok(hipMemcpy(dist, d_dist, (size_t)n * 8, hipMemcpyDeviceToHost)) ||
+        !ok(hipMemcpy(body, d_body, (size_t)n * 4, hipMemcpyDeviceToHost)) ||
+        !ok(hipMemcpy(c, cs, sizeof c, hipMemcpyDeviceToHost)) ||
+        !ok(hipMemset(cs, 0, RG_COUNTER_WORDS * sizeof(unsigned long long))))
+        return RG_ERR_DEVICE;
+    return rg_snap_status(c, nullptr);  // RG_OK without an error word
 }
 
 }  // extern "C"

@@ -1,14 +1,17 @@
 // rg_internal.h — host-side state behind the opaque rg_scene handle (what the description
 // determines is in rg_scene_tables.h, built without a device by rg_scene_build.cpp), shared
 // by rg_scene.hip (scene upload, replicas, kernel arguments), rg_launch.hip (per-stream
-// launch contexts, the tiled launch), rg_capi.hip (host-visible frames,
-// streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form), rg_ao.hip (the ambient occlusion pass), rg_ambient.hip (the ambient term), rg_frames.hip
-// (frames in flight over N processes), rg_multi.hip (one process driving N
+// launch contexts, the tiled launch, the launch path of the pixel passes: rg_frame_args,
+// rg_pass_check / rg_pass_enqueue, rg_pass_grid), rg_capi.hip (host-visible frames,
+// streaming, debug setters), rg_aa.hip (supersampled frames and their adaptive form),
+// rg_aov.hip (the AOV pass), rg_ao.hip (the ambient occlusion pass), rg_ambient.hip (the
+// ambient term), rg_frames.hip (frames in flight over N processes), rg_multi.hip (one process driving N
 // devices), rg_gather.hip (the pack and re-interleave kernels of both) and rg_rccl.hip
 // (the run-time RCCL loader, rg_rccl.h, and the rg_comm_* functions).  The band resource
 // set the two kinds of host frames are built on is in rg_bands.h, the band arithmetic in
-// rg_band_plan.h, the dealing of tiles to ranks and devices in rg_tile_deal.h.  Not part
-// of the ABI.
+// rg_band_plan.h, the dealing of tiles to ranks and devices in rg_tile_deal.h, the merge of
+// per-pass statistics in rg_stats_merge.h.  Defined here: rg_scratch (the device scratch of a
+// blocking entry) and rg_table_once (a device table made once per scene).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +28,7 @@
 #include "rg_device.h"
 #include "rg_lightbuf_ray.h"
 #include "rg_scene_tables.h"
+#include "rg_stats_merge.h"
 #include "rg_tile_deal.h"
 
 inline bool ok(hipError_t e) { return e == hipSuccess; }
@@ -137,7 +141,8 @@ struct rg_aa_res : rg_band_res {
     float pass_ms[5] = {0, 0, 0, 0, 0};
     uint32_t flagged = 0, listed_tiles = 0, bands_launched = 0;
     // the thin lens's tables on the device (rg_lens.h RG_LENS_TABLE_DOUBLES doubles): made on the first frame
-    // through a lens, never rewritten, so launches in flight may read them whatever the scene is given next
+    // through a lens (rg_table_once), never rewritten, so launches in flight may read them whatever the scene
+    // is given next
     double *d_lens = nullptr;
 };
 
@@ -190,7 +195,7 @@ struct rg_scene : rg_scene_facts, rg_scene_settings {
     int device = 0;
     // device tables: the host tables (host, shared with the replicas) uploaded to this device
     std::shared_ptr<const rg_host_tables> host;
-    std::vector<void *> allocations;
+    mutable std::vector<void *> allocations;  // freed with the scene: the tables below and rg_table_once's
     RgSph *sph = nullptr;
     double *sph_cc = nullptr;
     RgSphF *sphf = nullptr;
@@ -219,10 +224,10 @@ struct rg_scene : rg_scene_facts, rg_scene_settings {
     bool area_stale = false;
     double *d_area = nullptr;
     // the ambient occlusion pass's table on the device (rg_ao.h RG_AO_TABLE_DOUBLES doubles: every k's points,
-    // then the lens's rotations): made on the first AO frame (rg_ao.hip), never rewritten
+    // then the lens's rotations): made on the first AO frame (rg_ao.hip, rg_table_once), never rewritten
     mutable double *d_ao = nullptr;
     // the ambient term's share per body on the device (host->amb_share): made on the first ambient frame
-    // (rg_ambient.hip), never rewritten
+    // (rg_ambient.hip, rg_table_once), never rewritten
     mutable float *d_share = nullptr;
     // Settings of the host-visible and multi-device paths, read on the root scene only (not synced to replicas):
     int image_bands = 0;  // host-visible frames: 0 auto, -1 one launch writing host memory, -2 split, 1..16 row bands
@@ -351,6 +356,76 @@ rg_status rg_grow(rg_mem kind, size_t &cap, size_t want, std::initializer_list<r
 template <class T>
 rg_status rg_grow(rg_mem kind, T *&p, size_t &cap, size_t bytes) {  // one buffer, capacity in bytes
     return rg_grow(kind, cap, bytes, {{p, bytes}});
+}
+
+// rg_launch.hip: rg_make_args(s) plus what every launch of a frame sets: the context's counter sets (a launch
+// counts into set `cur`) and sticky word, the frame and its doubles, the tiling, out_rows, and the scene's camera
+// by value (the launch keeps it whatever the scene is given next).  The tile shape and the rest are the caller's.
+RgKernelArgs rg_frame_args(const rg_scene *s, rg_launch_ctx *cx, uint32_t W, uint32_t H, const rg_tiling &t,
+                           uint32_t tile_group, uint32_t out_rows);
+
+// rg_launch.hip: a pixel pass (one one-shot kernel over the tiles of a tiling: rg_aov.hip, rg_ao.hip) in two
+// steps.  rg_pass_check: the frame and the tiling (the first failing check decides the status), *rows = the
+// rows the tiling selects, the scene's device made current.  rg_pass_enqueue: the stream's launch context, the
+// frame's arguments with `tile_wlog`, launch(&args, payload, stream) unless rows == 0 (then nothing is enqueued
+// and the counter sets do not flip), and with `stats` the wait for the launch, its time and its counters
+// (without: no synchronisation).
+typedef hipError_t (*rg_pass_launch)(const RgKernelArgs *a, const void *payload, hipStream_t stream);
+rg_status rg_pass_check(const rg_scene *s, uint32_t W, uint32_t H, const rg_tiling *t, uint32_t *rows);
+rg_status rg_pass_enqueue(const rg_scene *s, uint32_t W, uint32_t H, const rg_tiling &t, uint32_t rows,
+                          hipStream_t stream, uint32_t tile_wlog, rg_stats *stats, rg_pass_launch launch,
+                          const void *payload);
+// rg_launch.hip: the one-shot grid of a pixel pass whose waves stride over the launch's tiles: blocks of `block`
+// threads (a tile per wave), at most blocks_per_cu per CU of the current device; *lds: the per-lane walk stacks.
+hipError_t rg_pass_grid(const RgKernelArgs &a, unsigned block, unsigned blocks_per_cu, dim3 *grid, size_t *lds);
+
+// The device scratch of a blocking entry point: allocate everything, return on status(), run the copies and
+// launches; the buffers are freed when the entry returns.  After a failed allocation (RG_ERR_OUT_OF_MEMORY, the
+// runtime's last error cleared) dev() allocates nothing more.
+class rg_scratch {
+    void *buf[8];
+    int n = 0;
+    rg_status st = RG_OK;
+
+public:
+    rg_scratch() = default;
+    rg_scratch(const rg_scratch &) = delete;
+    rg_scratch &operator=(const rg_scratch &) = delete;
+    ~rg_scratch() {
+        while (n > 0) (void)hipFree(buf[--n]);
+    }
+    template <class T>
+    T *dev(size_t bytes) {
+        void *p = nullptr;
+        if (st != RG_OK || n == 8 || !ok(hipMalloc(&p, bytes))) {
+            if (st == RG_OK) (void)hipGetLastError();
+            st = RG_ERR_OUT_OF_MEMORY;
+            return nullptr;
+        }
+        buf[n++] = p;
+        return static_cast<T *>(p);
+    }
+    rg_status status() const { return st; }
+};
+
+// A device table made once per scene and never rewritten, so launches in flight may read it whatever comes next:
+// nothing if `slot` is set; else `bytes` of device memory with `host` copied in (blocking: complete before the
+// first launch that reads it is enqueued; a null host copies nothing), freed with the scene.
+template <class T>
+rg_status rg_table_once(const rg_scene *s, T *&slot, const void *host, size_t bytes) {
+    if (slot) return RG_OK;
+    void *d = nullptr;
+    if (!ok(hipMalloc(&d, bytes))) {
+        (void)hipGetLastError();
+        return RG_ERR_OUT_OF_MEMORY;
+    }
+    if (host && !ok(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice))) {
+        (void)hipFree(d);
+        return RG_ERR_DEVICE;
+    }
+    s->allocations.push_back(d);
+    slot = static_cast<T *>(d);
+    return RG_OK;
 }
 
 // rg_scene.hip: RgKernelArgs::fov_adjustment of a field of view in degrees.

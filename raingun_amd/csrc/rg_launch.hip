@@ -1,6 +1,8 @@
 // rg_launch.hip — the tiled launch behind every render path: the per-stream
 // launch contexts (ray counters, error words, tile-order scratch, deep frame
-// buffer, primary-ray table), rg_launch_tiles (validate, fill the kernel
+// buffer, primary-ray table), the frame arguments every launch shares
+// (rg_frame_args), the launch path of the pixel passes (rg_pass_check,
+// rg_pass_enqueue, rg_pass_grid), rg_launch_tiles (validate, fill the kernel
 // arguments, size the deep frame buffer, refresh the primary-ray table, order
 // the tiles, launch and snapshot the counters), the decoding of counter
 // snapshots, and the device-resident entries of the C ABI
@@ -72,23 +74,10 @@ rg_status validate(const rg_scene *s, const rg_launch_desc &d, uint32_t *out_row
     return RG_OK;
 }
 
-// 2. The scene's arguments plus this launch's frame, tiling, outputs and counter sets.
+// 2. The frame's arguments (rg_frame_args) plus this launch's band, quotients, lens, area lights, outputs and ring.
 RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx *cx, uint32_t out_rows) {
-    RgKernelArgs a = rg_make_args(s);
-    a.counters = cx->counters + (size_t)cx->cur * RG_COUNTER_WORDS;  // zero (see rg_launch_ctx::counters)
-    a.counters_next = cx->counters + (size_t)(1 - cx->cur) * RG_COUNTER_WORDS;
-    a.err_sticky = cx->sticky;
-    a.width = d.width;
-    a.height = d.height;
-    a.tile_rows = d.tiling.tile_rows;
-    a.tile_stride = d.tiling.tile_stride;
-    a.tile_offset = d.tiling.tile_offset;
-    a.tile_group = d.tile_group;
+    RgKernelArgs a = rg_frame_args(s, cx, d.width, d.height, d.tiling, d.tile_group, out_rows);
     a.tile_base = d.tile_first;
-    a.out_rows = out_rows;
-    a.aspect = (double)d.width / (double)d.height;
-    a.width_d = (double)d.width;
-    a.height_d = (double)d.height;
     // the PLAIN kernels' camera quotients (rg_exact.h): every column and row of a frame size swept
     // once per launch context (n divisions for n pixels a side), then remembered
     if (cx->rdiv_w != d.width || cx->rdiv_h != d.height) {
@@ -99,16 +88,7 @@ RgKernelArgs fill_args(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx
     a.inv_w = 1.0 / a.width_d;
     a.inv_h = 1.0 / a.height_d;
     a.plain_veto = (cx->rdiv_ok && s->exact_div) ? 0u : 1u;
-    if (s->has_camera) {  // by value: this launch keeps its camera whatever the scene is given next
-        a.camera = 1u;
-        for (int k = 0; k < 3; ++k) {
-            a.cam_eye[k] = s->camera.eye[k];
-            a.cam_right[k] = s->camera.right[k];
-            a.cam_up[k] = s->camera.up[k];
-            a.cam_forward[k] = s->camera.forward[k];
-        }
-        a.plain_veto |= 4u;  // the PLAIN kernels' camera ray is the reference's view
-    }
+    if (a.camera) a.plain_veto |= 4u;  // the PLAIN kernels' camera ray is the reference's view
     if (rg_lens_active(s->lens.aperture, d.lens_k)) {  // by value, as the camera
         if (!a.camera) {  // the reference's view as a camera: the lens family is the camera family's
             a.camera = 1u;
@@ -283,6 +263,18 @@ rg_status launch_and_snapshot(const rg_launch_desc &d, rg_launch_ctx *cx, RgKern
     return RG_OK;
 }
 
+// The stats tail of a timed launch on cx's stream (ev0 .. ev1 recorded around it): wait for it, its time, the four
+// counter words of its set.
+rg_status stats_tail(rg_launch_ctx *cx, hipStream_t st, rg_stats *stats) {
+    unsigned long long c[4];
+    if (!ok(hipMemcpyAsync(c, cx->last_counters, sizeof c, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
+        return RG_ERR_DEVICE;
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, cx->ev0, cx->ev1);
+    stats->kernel_ms = ms;
+    return rg_snap_status(c, stats);
+}
+
 // The ABI's device-resident renders (a null tiling stays invalid: rg_tiling{} selects nothing).
 rg_launch_desc device_frame(uint32_t width, uint32_t height, const rg_tiling *tiling, uint8_t *rgba_dev,
                             float *rgb_dev, hipStream_t stream) {
@@ -360,6 +352,78 @@ rg_status rg_grow(rg_mem kind, size_t &cap, size_t want, std::initializer_list<r
     }
     cap = want;
     return RG_OK;
+}
+
+RgKernelArgs rg_frame_args(const rg_scene *s, rg_launch_ctx *cx, uint32_t W, uint32_t H, const rg_tiling &t,
+                           uint32_t tile_group, uint32_t out_rows) {
+    RgKernelArgs a = rg_make_args(s);
+    a.counters = cx->counters + (size_t)cx->cur * RG_COUNTER_WORDS;  // zero (see rg_launch_ctx::counters)
+    a.counters_next = cx->counters + (size_t)(1 - cx->cur) * RG_COUNTER_WORDS;
+    a.err_sticky = cx->sticky;
+    a.width = W;
+    a.height = H;
+    a.tile_rows = t.tile_rows;
+    a.tile_stride = t.tile_stride;
+    a.tile_offset = t.tile_offset;
+    a.tile_group = tile_group;
+    a.out_rows = out_rows;
+    a.width_d = (double)W;
+    a.height_d = (double)H;
+    a.aspect = a.width_d / a.height_d;
+    if (s->has_camera) {  // by value: this launch keeps its camera whatever the scene is given next
+        a.camera = 1u;
+        for (int k = 0; k < 3; ++k) {
+            a.cam_eye[k] = s->camera.eye[k];
+            a.cam_right[k] = s->camera.right[k];
+            a.cam_up[k] = s->camera.up[k];
+            a.cam_forward[k] = s->camera.forward[k];
+        }
+    }
+    return a;
+}
+
+rg_status rg_pass_check(const rg_scene *s, uint32_t W, uint32_t H, const rg_tiling *t, uint32_t *rows) {
+    if (!s || W == 0 || H == 0 || !t || !rg_tiling_valid(t)) return RG_ERR_INVALID_ARGUMENT;
+    if (W < H) return RG_ERR_PORTRAIT;  // ray.rs:42
+    *rows = rg_tiling_rows(H, t);
+    if ((unsigned long long)*rows * W >= (1ull << 32) || (unsigned long long)H * W >= (1ull << 32))
+        return RG_ERR_INVALID_ARGUMENT;  // the reference's u32 pixel index (rendering.rs:27)
+    return ok(hipSetDevice(s->device)) ? RG_OK : RG_ERR_DEVICE;
+}
+
+rg_status rg_pass_enqueue(const rg_scene *s, uint32_t W, uint32_t H, const rg_tiling &t, uint32_t rows,
+                          hipStream_t stream, uint32_t tile_wlog, rg_stats *stats, rg_pass_launch launch,
+                          const void *payload) {
+    rg_launch_ctx *cx = rg_ctx_for(s, stream);
+    if (!cx) return RG_ERR_OUT_OF_MEMORY;
+    s->last = cx;
+    RgKernelArgs a = rg_frame_args(s, cx, W, H, t, 1u, rows);
+    a.tile_wlog = tile_wlog;
+    cx->last_counters = a.counters;
+    cx->last_plain = 0;
+    cx->last_shvol = 0;
+    if (stats && !ok(hipEventRecord(cx->ev0, stream))) return RG_ERR_DEVICE;
+    if (rows > 0) {
+        if (!ok(launch(&a, payload, stream))) return RG_ERR_DEVICE;
+        cx->cur = 1 - cx->cur;  // the kernel zeroes the other set for the next launch
+    }
+    if (!stats) return RG_OK;
+    if (!ok(hipEventRecord(cx->ev1, stream))) return RG_ERR_DEVICE;
+    return stats_tail(cx, stream, stats);
+}
+
+hipError_t rg_pass_grid(const RgKernelArgs &a, unsigned block, unsigned blocks_per_cu, dim3 *grid, size_t *lds) {
+    int dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long ntiles = rg_tile_count(a), per_block = block / 64u;
+    const unsigned long long want = (ntiles + per_block - 1ull) / per_block;
+    const unsigned long long cap = (unsigned long long)(cus > 0 ? cus : 1) * blocks_per_cu;
+    *grid = dim3((unsigned)(want < cap ? want : cap));
+    // per-lane walk stacks (stride = block size): lane_stack entries + the spare slot (rg_k_bvh.h bvh_lane)
+    *lds = a.lane_stack > 0 ? ((size_t)(a.lane_stack + 1) * 4u) * block : 0u;
+    return hipSuccess;
 }
 
 rg_status rg_launch_tiles(const rg_scene *s, const rg_launch_desc &d, rg_launch_ctx **ctx_out) {
@@ -457,13 +521,7 @@ rg_status rg_render_tiles_async(const rg_scene *s, uint32_t width, uint32_t heig
     d.timed = stats != nullptr;
     rg_status r = rg_launch_tiles(s, d, &cx);
     if (r != RG_OK || !stats) return r;
-    unsigned long long c[4];
-    if (!ok(hipMemcpyAsync(c, cx->last_counters, sizeof c, hipMemcpyDeviceToHost, st))) return RG_ERR_DEVICE;
-    if (!ok(hipStreamSynchronize(st))) return RG_ERR_DEVICE;
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, cx->ev0, cx->ev1);
-    stats->kernel_ms = ms;
-    return rg_snap_status(c, stats);
+    return stats_tail(cx, st, stats);
 }
 
 rg_status rg_render_tiles_pipelined(const rg_scene *s, uint32_t width, uint32_t height, const rg_tiling *tiling,

@@ -46,13 +46,10 @@ void release(rg_scene *s) {
     rg_multi_release(s);
     rg_image_res_release(s->img);
     rg_aa_res_release(s->aa);
+    rg_ambient_release(s, nullptr, true);
+    // after the resource sets, whose release waits for their streams: the scene's tables and the make-once ones
     for (void *p : s->allocations) (void)hipFree(p);
     s->allocations.clear();
-    if (s->d_ao) (void)hipFree(s->d_ao);
-    s->d_ao = nullptr;
-    rg_ambient_release(s, nullptr, true);
-    if (s->d_share) (void)hipFree(s->d_share);
-    s->d_share = nullptr;
     if (s->lds_blob) (void)hipFree(s->lds_blob);
     s->lds_blob = nullptr;
     for (rg_launch_ctx *c : s->ctxs) rg_ctx_destroy(c);

@@ -228,6 +228,47 @@ def test_three_streams_in_flight(example_scenes, name):
         ds.close()
 
 
+@pytest.mark.parametrize("with_stats", [True, False], ids=["stats", "no_stats"])
+def test_tiling_that_selects_no_row(example_scenes, with_stats):
+    """16x8 under tiling (8, 2, 1): the frame has tile 0 alone, the tiling takes tiles 1, 3, ..  RG_OK, no ray,
+    no store, and nothing enqueued: the counter sets must not flip, or the next launch on the stream would count
+    on top of what the frame before left in the other set."""
+    import torch
+
+    name, w, h = "test1", 16, 8
+    scene = ao_cases.scene(example_scenes, name)
+    k, radius, bias = ao_cases.combos(name)[1]
+    ref = ao_cases.ref(example_scenes, name, w, h, k, radius, bias)
+    ds = DeviceScene(scene)
+    stream = torch.cuda.Stream()
+    hs = stream.cuda_stream
+    try:
+        def frame(what):
+            st = _abi.rg_stats()
+            got = ds.render_ao_tiles(w, h, k, radius, bias, stream=hs, stats=st)
+            stream.synchronize()
+            _assert_frame(got.cpu().numpy(), st, ref, what)
+
+        frame("the frame before")  # its counts stay in the set the next launch zeroes
+        big = torch.full((4096,), CANARY, dtype=torch.uint8, device="cuda")
+        v = _abi.rg_ao(k, 0, radius, bias)
+        t = _abi.rg_tiling(8, 2, 1)
+        assert _abi.lib().rg_tiling_rows(h, C.byref(t)) == 0
+        st = _abi.rg_stats()
+        st.rays.primary, st.error_pixel = 77, 5
+        status = _abi.lib().rg_render_ao_async(ds.handle, w, h, C.byref(t), C.byref(v), C.c_void_p(big.data_ptr() + 2048),
+                                               C.c_void_p(hs), C.byref(st) if with_stats else None)
+        assert status == _abi.RG_OK
+        if with_stats:
+            assert st.rays.as_dict() == {"primary": 0, "shadow": 0, "secondary": 0} and st.error_pixel == -1
+        frame("the frame after")
+        assert bool((big == CANARY).all()), "a store under a tiling that selects nothing"
+        assert ds.stream_status(hs) == (_abi.RG_OK, -1)
+    finally:
+        ds.release_stream(hs)
+        ds.close()
+
+
 # ---------------------------------------------------------------- canary
 @pytest.mark.parametrize("tiling", [(H, 1, 0), (8, 3, 1)])
 def test_stores_stay_inside_the_output(example_scenes, tiling):

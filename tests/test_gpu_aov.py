@@ -217,8 +217,49 @@ def test_three_cameras_in_flight(example_scenes, name):
         ds.close()
 
 
+@pytest.mark.parametrize("with_stats", [True, False], ids=["stats", "no_stats"])
+def test_tiling_that_selects_no_row(example_scenes, with_stats):
+    """16x8 under tiling (8, 2, 1): the frame has tile 0 alone, the tiling takes tiles 1, 3, ..  RG_OK, no ray,
+    no store, and nothing enqueued: the counter sets must not flip, or the next launch on the stream would count
+    on top of what the frame before left in the other set."""
+    import torch
+
+    name, w, h = "test1", 16, 8
+    scene = _scene(example_scenes, name)
+    _, ref, counts, _ = _ref(example_scenes, name, w, h)
+    ds = DeviceScene(scene)
+    stream = torch.cuda.Stream()
+    hs = stream.cuda_stream
+    try:
+        def frame(what):
+            st = _abi.rg_stats()
+            got = ds.render_aov_tiles(w, h, stream=hs, stats=st)
+            stream.synchronize()
+            _assert_layers(scene, {n: t.cpu().numpy() for n, t in got.items()}, ref, what)
+            assert st.rays.as_dict() == counts and st.error_pixel == -1, what
+
+        frame("the frame before")  # its counts stay in the set the next launch zeroes
+        big = torch.full((5 * 4096,), CANARY, dtype=torch.uint8, device="cuda")
+        v = _abi.rg_aov(**{n: big.data_ptr() + 4096 * i for i, n in enumerate(aov.LAYERS)})
+        t = _abi.rg_tiling(8, 2, 1)
+        assert _abi.lib().rg_tiling_rows(h, C.byref(t)) == 0
+        st = _abi.rg_stats()
+        st.rays.primary, st.error_pixel = 77, 5
+        status = _abi.lib().rg_render_aov_async(ds.handle, w, h, C.byref(t), C.byref(v), C.c_void_p(hs),
+                                                C.byref(st) if with_stats else None)
+        assert status == _abi.RG_OK
+        if with_stats:
+            assert st.rays.as_dict() == {"primary": 0, "shadow": 0, "secondary": 0} and st.error_pixel == -1
+        frame("the frame after")
+        assert bool((big == CANARY).all()), "a store under a tiling that selects nothing"
+        assert ds.stream_status(hs) == (_abi.RG_OK, -1)
+    finally:
+        ds.release_stream(hs)
+        ds.close()
+
+
 # ---------------------------------------------------------------- layer subsets
-SUBSETS = [(n,) for n in aov.LAYERS] + [("body", "depth")]
+SUBSETS =[(n,) for n in aov.LAYERS] + [("body", "depth")]
 CANARY = 0xA5
 
 
