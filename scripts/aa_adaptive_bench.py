@@ -24,14 +24,11 @@ import ctypes as C
 import json
 import statistics
 import sys
-from pathlib import Path
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO))
+import rg_measure as rm
+from rg_measure import REPO, summary
 
-
-def _summary(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "reps": len(ms)}
+SCENES = {"test1": "test1", "synth1024": "north_star_1024_spheres"}  # --scenes name -> rg_measure.bench_scenes()
 
 
 def main(argv=None) -> int:
@@ -42,36 +39,27 @@ def main(argv=None) -> int:
     ap.add_argument("--scenes", default="test1,synth1024")
     ap.add_argument("--samples", default="2,4")
     ap.add_argument("--thresholds", default="16,32,64")
-    ap.add_argument("--reps", type=int, default=9, help="timed repetitions per variant (the median is reported)")
+    ap.add_argument("--reps", "--batches", dest="batches", type=int, default=9,
+                    help="timed repetitions per variant (the median is reported)")
     ap.add_argument("--warmup", type=int, default=2, help="untimed repetitions first")
     ap.add_argument("--band-rows", type=int, default=0, help="rg_debug_set_aa_band_rows (0: automatic)")
     ap.add_argument("--full-only", action="store_true",
                     help="only (a) and (b): the figures an older build gives too (the full form did not move)")
     args = ap.parse_args(argv)
+    args.per_batch = 1  # `timed` below times one call
 
     import torch
 
     from raingun_amd import _abi
-    from raingun_amd.scene import DeviceScene, load_scene
-    from raingun_amd.synth import synthetic_yaml
+    from raingun_amd.scene import DeviceScene
 
-    if not torch.cuda.is_available():
-        raise SystemExit("aa_adaptive_bench.py needs a GPU: nothing is measured without one")
+    rm.require_gpu("aa_adaptive_bench.py")
     lib = _abi.lib()
     adaptive = hasattr(lib, "rg_render_aa_adaptive") and not args.full_only
     W, H = args.width, args.height
     stream = torch.cuda.Stream()
     hs = C.c_void_p(stream.cuda_stream)
-    golden = REPO / "tests" / "golden"
-
-    def load(name):
-        if name == "test1":
-            scene = load_scene(golden / "examples" / "test1.yml", texture_root=golden)
-            scene.max_recursion_depth = 5
-            return scene
-        if name == "synth1024":  # the north-star scene of bench.py: 1024 spheres + 2 planes, depth 5
-            return load_scene(synthetic_yaml(1024, 2, 5))
-        raise SystemExit(f"unknown scene {name}")
+    scenes = rm.bench_scenes()
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -81,13 +69,14 @@ def main(argv=None) -> int:
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    result = {"device": torch.cuda.get_device_name(0), "width": W, "height": H, "max_depth": 5, "reps": args.reps,
-              "band_rows": args.band_rows, "configs": []}
+    result = {**rm.header(args, W, H), "max_depth": 5, "band_rows": args.band_rows, "configs": []}
     rgba = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda")
     mask = torch.empty((H, W), dtype=torch.uint8, device="cuda")
-    whole = _abi.rg_tiling(H, 1, 0)
     for name in args.scenes.split(","):
-        ds = DeviceScene(load(name))
+        if name not in SCENES:
+            raise SystemExit(f"unknown scene {name}")
+        ds = DeviceScene(scenes[SCENES[name]])
+        la = rm.Launches(ds, W, H, stream)
         ds.set_aa_band_rows(args.band_rows)
         if adaptive:
             _abi.check(lib.rg_debug_set_aa_adaptive_timing(ds.handle, 1))
@@ -96,17 +85,17 @@ def main(argv=None) -> int:
                 st = {v: _abi.rg_stats() for v in "abc"}
 
                 def one(stats=None):
-                    _abi.check(lib.rg_render_tiles_async(ds.handle, W, H, C.byref(whole), C.c_void_p(rgba.data_ptr()),
-                                                         None, hs, stats))
+                    la.frame(rgba, stats=stats)
                     stream.synchronize()
 
                 def full(stats=None):
-                    _abi.check(lib.rg_render_aa_async(ds.handle, W, H, k, C.c_void_p(rgba.data_ptr()), None, hs, stats))
+                    la.aa(k, rgba, stats=stats)
                     stream.synchronize()
 
                 def adapt(stats=None):
                     _abi.check(lib.rg_render_aa_adaptive(ds.handle, W, H, k, T, C.c_void_p(rgba.data_ptr()), None,
-                                                         C.c_void_p(mask.data_ptr()), hs, stats))
+                                                         C.c_void_p(mask.data_ptr()), hs,
+                                                         C.byref(stats) if stats is not None else None))
 
                 fns = {"a_one_sample": one, "b_full": full}
                 if adaptive:
@@ -116,20 +105,20 @@ def main(argv=None) -> int:
                         fn()
                 ms = {v: [] for v in fns}
                 passes = []
-                for _ in range(args.reps):
+                for _ in range(args.batches):
                     for v, fn in fns.items():
                         ms[v].append(timed(fn))
                         if v == "c_adaptive":
                             p = (C.c_float * 5)()
                             _abi.check(lib.rg_debug_aa_adaptive_info(ds.handle, p, None, None, None))
                             passes.append(list(p))
-                one(C.byref(st["a"]))
-                full(C.byref(st["b"]))
+                one(st["a"])
+                full(st["b"])
                 cfg = {"scene": name, "samples": k, "threshold": T,
-                       "a_one_sample": _summary(ms["a_one_sample"]), "b_full": _summary(ms["b_full"]),
+                       "a_one_sample": summary(ms["a_one_sample"]), "b_full": summary(ms["b_full"]),
                        "rays_a": st["a"].rays.as_dict(), "rays_b": st["b"].rays.as_dict()}
                 if adaptive:
-                    adapt(C.byref(st["c"]))
+                    adapt(st["c"])
                     flagged, tiles, bands = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
                     _abi.check(lib.rg_debug_aa_adaptive_info(ds.handle, None, C.byref(flagged), C.byref(tiles),
                                                              C.byref(bands)))
@@ -139,7 +128,7 @@ def main(argv=None) -> int:
                     a, b, c = (statistics.median(ms[v]) for v in ("a_one_sample", "b_full", "c_adaptive"))
                     med = [statistics.median(p[i] for p in passes) for i in range(5)]
                     cfg.update({
-                        "c_adaptive": _summary(ms["c_adaptive"]), "rays_c": st["c"].rays.as_dict(),
+                        "c_adaptive": summary(ms["c_adaptive"]), "rays_c": st["c"].rays.as_dict(),
                         "flagged": flagged.value, "flagged_share": share, "listed_tiles": tiles.value,
                         "tiles_of_sample_frame": ((k * W + 7) // 8) * ((k * H + 7) // 8), "bands_launched": bands.value,
                         "passes_median_ms": dict(zip(("one_sample", "mask", "list", "sparse_renders_sum",
@@ -151,9 +140,7 @@ def main(argv=None) -> int:
                 print(json.dumps(cfg), flush=True)
         ds.close()
 
-    outp = Path(args.out)
-    outp.parent.mkdir(parents=True, exist_ok=True)
-    outp.write_text(json.dumps(result, indent=1) + "\n")
+    rm.write_record(result, args.out, echo=False)  # each configuration was printed as it finished
     return 0
 
 

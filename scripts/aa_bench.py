@@ -20,26 +20,19 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
+import functools
 import statistics
 import sys
 import time
-from pathlib import Path
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO))
-
-
-def _summary(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "batches": len(ms)}
+import rg_measure as rm
+from rg_measure import REPO, summary
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=str(REPO / "profiles" / "aa" / "aa_bench.json"))
-    ap.add_argument("--batches", type=int, default=7, help="timed batches per variant (the median is reported)")
-    ap.add_argument("--per-batch", type=int, default=10, help="launches or frames per timed batch")
-    ap.add_argument("--warmup", type=int, default=3, help="untimed batches first")
+    rm.add_timing_args(ap, batches=7, per_batch=10, warmup=3)
     ap.add_argument("--band-rows", type=int, default=0, help="rg_debug_set_aa_band_rows (0: automatic)")
     ap.add_argument("--skip-resolve", action="store_true", help="only the render measurements (band-size sweeps)")
     args = ap.parse_args(argv)
@@ -48,10 +41,9 @@ def main(argv=None) -> int:
     import torch
 
     from raingun_amd import _abi
-    from raingun_amd.scene import DeviceScene, load_scene
+    from raingun_amd.scene import DeviceScene
 
-    if not torch.cuda.is_available():
-        raise SystemExit("aa_bench.py needs a GPU: nothing is measured without one")
+    rm.require_gpu("aa_bench.py")
     lib = _abi.lib()
     lib.rg_launch_resolve.restype = C.c_int
     lib.rg_launch_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -60,29 +52,9 @@ def main(argv=None) -> int:
     stream = torch.cuda.Stream()
     hs = C.c_void_p(stream.cuda_stream)
 
-    def batch_ms(fn):
-        """HIP-event time of per_batch calls of fn on `stream`, per call."""
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(args.per_batch):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.per_batch
-
-    def alternate(fns):
-        """Each of fns warmed up, then timed `batches` times, one batch of each in turn."""
-        for fn in fns.values():
-            for _ in range(args.warmup):
-                batch_ms(fn)
-        res = {k: [] for k in fns}
-        for _ in range(args.batches):
-            for k, fn in fns.items():
-                res[k].append(batch_ms(fn))
-        return res
-
-    result = {"device": torch.cuda.get_device_name(0), "per_batch": args.per_batch, "batches": args.batches,
-              "resolve": [], "render": {}}
+    alternate = functools.partial(rm.alternate, batch_ms=rm.event_batch_ms(stream, args.per_batch),
+                                  warmup=args.warmup, batches=args.batches)
+    result = {**rm.header(args), "resolve": [], "render": {}}
 
     # ---------------------------------------------------------------- 1. the resolve kernel alone
     W, H = 3840, 2160
@@ -112,7 +84,7 @@ def main(argv=None) -> int:
             result["resolve"].append({
                 "width": W, "height": H, "samples": k, "f32_output": want_rgb,
                 "bytes_read": read_b, "bytes_written": write_b,
-                "resolve": _summary(r["resolve"]), "copy_same_traffic": _summary(r["copy"]),
+                "resolve": summary(r["resolve"]), "copy_same_traffic": summary(r["copy"]),
                 "resolve_tb_per_s": (read_b + write_b) / (res_ms * 1e-3) / 1e12,
                 "copy_tb_per_s": 2 * copy_b / (copy_ms * 1e-3) / 1e12,
                 "resolve_over_copy": res_ms / copy_ms,
@@ -122,32 +94,21 @@ def main(argv=None) -> int:
         torch.cuda.empty_cache()
 
     # ---------------------------------------------------------------- 2. / 3. the render
-    golden = REPO / "tests" / "golden"
-    scene = load_scene(golden / "examples" / "test1.yml", texture_root=golden)
-    scene.max_recursion_depth = 5
-    ds = DeviceScene(scene)
+    ds = DeviceScene(rm.bench_scenes()["test1"])
     ds.set_aa_band_rows(args.band_rows)
     w, h, k = 1920, 1080, 2
     aa_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
     big_rgba = torch.empty((k * h, k * w, 4), dtype=torch.uint8, device="cuda")
-    whole = _abi.rg_tiling(k * h, 1, 0)
-
-    def aa_async():
-        _abi.check(lib.rg_render_aa_async(ds.handle, w, h, k, C.c_void_p(aa_rgba.data_ptr()), None, hs, None))
-
-    def plain_async():
-        _abi.check(lib.rg_render_tiles_async(ds.handle, k * w, k * h, C.byref(whole), C.c_void_p(big_rgba.data_ptr()),
-                                             None, hs, None))
-
-    r = alternate({"aa": aa_async, "plain": plain_async})
+    out_size, sample_size = rm.Launches(ds, w, h, stream), rm.Launches(ds, k * w, k * h, stream)
+    r = alternate({"aa": lambda: out_size.aa(k, aa_rgba), "plain": lambda: sample_size.frame(big_rgba)})
     aa_ms, plain_ms = statistics.median(r["aa"]), statistics.median(r["plain"])
     st = _abi.rg_stats()
-    _abi.check(lib.rg_render_aa_async(ds.handle, w, h, k, C.c_void_p(aa_rgba.data_ptr()), None, hs, C.byref(st)))
+    out_size.aa(k, aa_rgba, stats=st)
     result["render"] = {
         "scene": "test1", "max_depth": 5, "width": w, "height": h, "samples": k, "band_rows": args.band_rows,
         "rays": st.rays.total(),
-        "rg_render_aa_async": _summary(r["aa"]),
-        "rg_render_tiles_async_at_sample_size": _summary(r["plain"]),
+        "rg_render_aa_async": summary(r["aa"]),
+        "rg_render_tiles_async_at_sample_size": summary(r["plain"]),
         "scratch_and_resolve_ms": aa_ms - plain_ms,
         "stats_kernel_ms_one_frame": st.kernel_ms,
     }
@@ -167,10 +128,7 @@ def main(argv=None) -> int:
                                                      "max_ms": max(host_ms), "calls": len(host_ms)}
     ds.close()
 
-    outp = Path(args.out)
-    outp.parent.mkdir(parents=True, exist_ok=True)
-    outp.write_text(json.dumps(result, indent=1) + "\n")
-    print(json.dumps(result))
+    rm.write_record(result, args.out)
     return 0
 
 

@@ -22,14 +22,12 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import json
-import os
-import statistics
 import subprocess
 import sys
 from pathlib import Path
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO))
+import rg_measure as rm
+from rg_measure import REPO, summary
 PROFILES = REPO / "profiles" / "ambient"
 INF = float("inf")
 FINITE = {"test1": 8.0, "north_star_1024_spheres": 16.0}
@@ -45,10 +43,6 @@ def build_floor():
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-o",
                         str(FLOOR_LIB), str(FLOOR_SRC)], check=True)
     return FLOOR_LIB
-
-
-def _summary(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "batches": len(ms)}
 
 
 def _fmt(r):
@@ -86,13 +80,8 @@ def _readme(result, profiles=PROFILES) -> str:
     if not f.exists():
         lines += ["A/B of the kernel's open choices: not measured.", ""]
     else:
-        ab = json.loads(f.read_text())
-        cols = sorted({s for v in ab.values() for s in v})
         lines += ["## A/B of the filter kernel's open choices (`ab_filter.json`; median ms per launch)", "",
-                  "| build | " + " | ".join(cols) + " |", "|---|" + "---|" * len(cols)]
-        for key, v in ab.items():
-            lines.append(f"| {key} | " + " | ".join(f"{v[s]['median_ms']:.3f}" if s in v else "" for s in cols) + " |")
-        lines.append("")
+                  *rm.ab_table(json.loads(f.read_text()))]
     return "\n".join(lines)
 
 
@@ -101,9 +90,7 @@ def main(argv=None) -> int:
     ap.add_argument("--dir", default=str(PROFILES), help="where the records live (default profiles/ambient)")
     ap.add_argument("--out", default=None, help="the JSON document (default DIR/ambient_bench.json)")
     ap.add_argument("--label", default="default build")
-    ap.add_argument("--batches", type=int, default=7, help="timed batches per variant (the median is reported)")
-    ap.add_argument("--per-batch", type=int, default=5, help="launches per timed batch")
-    ap.add_argument("--warmup", type=int, default=1, help="untimed batches first")
+    rm.add_timing_args(ap, batches=7, per_batch=5, warmup=1)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--ab", metavar="FILE", help="A/B run: the filter alone, stored under --key in DIR/FILE")
@@ -123,11 +110,9 @@ def main(argv=None) -> int:
     import torch
 
     from raingun_amd import _abi, ambient
-    from raingun_amd.scene import DeviceScene, load_scene
-    from raingun_amd.synth import synthetic_scene
+    from raingun_amd.scene import DeviceScene
 
-    if not torch.cuda.is_available():
-        raise SystemExit("ambient_bench.py needs a GPU: nothing is measured without one")
+    rm.require_gpu("ambient_bench.py")
     lib = _abi.lib()
     floor = None
     if not args.ab:
@@ -141,33 +126,14 @@ def main(argv=None) -> int:
     hs = C.c_void_p(stream.cuda_stream)
     W, H = args.width, args.height
     npx = W * H
-    whole = _abi.rg_tiling(H, 1, 0)
+    batch_ms = rm.event_batch_ms(stream, args.per_batch)
 
-    def batch_ms(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(args.per_batch):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.per_batch
+    def measured(fns):
+        """The variants alternating -> {name: summary}, the rows of the record."""
+        return {k: summary(v) for k, v in rm.alternate(fns, batch_ms, args.warmup, args.batches).items()}
 
-    def alternate(fns):
-        for fn in fns.values():
-            for _ in range(args.warmup):
-                batch_ms(fn)
-        res = {k: [] for k in fns}
-        for _ in range(args.batches):
-            for k, fn in fns.items():
-                res[k].append(batch_ms(fn))
-        return {k: _summary(v) for k, v in res.items()}
-
-    result = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("RAINGUN_HIP_LIB", "raingun_amd/libraingun_hip.so"),
-              "label": args.label, "per_batch": args.per_batch, "batches": args.batches, "width": W, "height": H, "scenes": {}}
-    golden = REPO / "tests" / "golden"
-    test1 = load_scene(golden / "examples" / "test1.yml", texture_root=golden)
-    test1.max_recursion_depth = 5
-    scenes = {"test1": test1, "north_star_1024_spheres": synthetic_scene(1024, 2, 5)}
+    result = {**rm.header(args, W, H), "scenes": {}}
+    scenes = rm.bench_scenes()
     f32 = dict(dtype=torch.float32, device="cuda")
     raw, aof = torch.empty((H, W), **f32), torch.empty((H, W), **f32)
     body = torch.empty((H, W), dtype=torch.int32, device="cuda")
@@ -182,16 +148,16 @@ def main(argv=None) -> int:
             ds = DeviceScene(scene)
             share = torch.from_numpy(np.ascontiguousarray(ambient.shares(scene))).cuda()
 
+            la = rm.Launches(ds, W, H, stream)
+
             def launch_ao(k, radius=INF, stats=None):
-                v = _abi.rg_ao(k, 0, radius, 1e-13)
-                _abi.check(lib.rg_render_ao_async(ds.handle, W, H, C.byref(whole), C.byref(v), p(raw), hs,
-                                                  C.byref(stats) if stats is not None else None))
+                la.ao(_abi.rg_ao(k, 0, radius, 1e-13), raw, stats)
 
             def launch_aov():
-                _abi.check(lib.rg_render_aov_async(ds.handle, W, H, C.byref(whole), C.byref(layers), hs, None))
+                la.aov(layers)
 
             def launch_beauty():
-                _abi.check(lib.rg_render_aa_async(ds.handle, W, H, 1, p(rgba), p(rgb), hs, None))
+                la.aa(1, rgba, rgb)
 
             def launch_filter(r, nmin=0.9):
                 f = _abi.rg_ao_filter_desc(r, nmin)
@@ -213,15 +179,15 @@ def main(argv=None) -> int:
             row = {"hit_fraction": int(st.rays.shadow) / 16 / npx}
             fns = {f"filter_r{r}": (lambda r=r: launch_filter(r)) for r in RADII}
             if args.ab:
-                row.update(alternate(fns))
+                row.update(measured(fns))
             else:
                 fns["filter_floor"] = lambda: floor.ambient_floor_filter(p(raw), p(body), p(normal), p(aof), npx, hs)
-                row.update(alternate(fns))
+                row.update(measured(fns))
                 launch_filter(2)
-                row.update(alternate({
+                row.update(measured({
                     "compose": launch_compose,
                     "compose_floor": lambda: floor.ambient_floor_compose(p(rgb), p(albedo), p(body), p(aof), p(rgba), npx, hs)}))
-                row.update(alternate({
+                row.update(measured({
                     "ambient_frame_k2": lambda: launch_ambient(2), "ambient_frame_k4": lambda: launch_ambient(4),
                     "beauty_samples1_rgb": launch_beauty, "aov_body_normal_albedo": launch_aov,
                     "ao_k2_inf": lambda: launch_ao(2), "ao_k4_inf": lambda: launch_ao(4), "ao_k8_inf": lambda: launch_ao(8),
@@ -246,10 +212,7 @@ def main(argv=None) -> int:
         f.write_text(json.dumps(ab, indent=1) + "\n")
         print(json.dumps({key: {k: round(v["median_ms"], 4) for k, v in ab[key].items()}}))
         return 0
-    outp = Path(args.out)
-    outp.parent.mkdir(parents=True, exist_ok=True)
-    outp.write_text(json.dumps(result, indent=1) + "\n")
-    print(json.dumps(result))
+    rm.write_record(result, args.out)
     if args.readme:
         (profiles / "README.md").write_text(_readme(result, profiles))
     return 0

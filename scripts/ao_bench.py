@@ -20,22 +20,16 @@ build, same box, back to back.
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import json
-import os
 import statistics
 import sys
 from pathlib import Path
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO))
+import rg_measure as rm
+from rg_measure import REPO, summary
 PROFILES = REPO / "profiles" / "ao"
 INF = float("inf")
 FINITE = {"test1": 8.0, "north_star_1024_spheres": 16.0}
-
-
-def _summary(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "batches": len(ms)}
 
 
 def _readme(result, PROFILES=PROFILES) -> str:
@@ -70,12 +64,7 @@ def _readme(result, PROFILES=PROFILES) -> str:
             lines += [f"A/B {what}: not measured.", ""]
             continue
         ab = json.loads(f.read_text())
-        lines += [f"A/B {what} (`{fname}`; AO k = 4, median ms per frame):", ""]
-        scenes = sorted({s for v in ab.values() for s in v})
-        lines += ["| build | " + " | ".join(scenes) + " |", "|---|" + "---|" * len(scenes)]
-        for key, v in ab.items():
-            lines.append(f"| {key} | " + " | ".join(f"{v[s]['median_ms']:.3f}" if s in v else "" for s in scenes) + " |")
-        lines.append("")
+        lines += [f"A/B {what} (`{fname}`; AO k = 4, median ms per frame):", "", *rm.ab_table(ab)]
     return "\n".join(lines)
 
 
@@ -84,9 +73,7 @@ def main(argv=None) -> int:
     ap.add_argument("--dir", default=str(PROFILES), help="where the records live (default profiles/ao)")
     ap.add_argument("--out", default=None, help="the JSON document (default DIR/ao_bench.json)")
     ap.add_argument("--label", default="default build")
-    ap.add_argument("--batches", type=int, default=5, help="timed batches per variant (the median is reported)")
-    ap.add_argument("--per-batch", type=int, default=3, help="launches per timed batch")
-    ap.add_argument("--warmup", type=int, default=1, help="untimed batches first")
+    rm.add_timing_args(ap, batches=5, per_batch=3, warmup=1)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--ab", metavar="FILE", help="A/B run: AO alone (k = 4), stored under --key in profiles/ao/FILE")
@@ -105,42 +92,14 @@ def main(argv=None) -> int:
     import torch
 
     from raingun_amd import _abi
-    from raingun_amd.scene import DeviceScene, load_scene
-    from raingun_amd.synth import synthetic_scene
+    from raingun_amd.scene import DeviceScene
 
-    if not torch.cuda.is_available():
-        raise SystemExit("ao_bench.py needs a GPU: nothing is measured without one")
-    lib = _abi.lib()
+    rm.require_gpu("ao_bench.py")
     stream = torch.cuda.Stream()
-    hs = C.c_void_p(stream.cuda_stream)
     W, H = args.width, args.height
-    whole = _abi.rg_tiling(H, 1, 0)
-
-    def batch_ms(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(args.per_batch):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.per_batch
-
-    def alternate(fns):
-        for fn in fns.values():
-            for _ in range(args.warmup):
-                batch_ms(fn)
-        res = {k: [] for k in fns}
-        for _ in range(args.batches):
-            for k, fn in fns.items():
-                res[k].append(batch_ms(fn))
-        return res
-
-    result = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("RAINGUN_HIP_LIB", "raingun_amd/libraingun_hip.so"),
-              "label": args.label, "per_batch": args.per_batch, "batches": args.batches, "width": W, "height": H, "scenes": {}}
-    golden = REPO / "tests" / "golden"
-    test1 = load_scene(golden / "examples" / "test1.yml", texture_root=golden)
-    test1.max_recursion_depth = 5
-    scenes = {"test1": test1, "north_star_1024_spheres": synthetic_scene(1024, 2, 5)}
+    batch_ms = rm.event_batch_ms(stream, args.per_batch)
+    result = {**rm.header(args, W, H), "scenes": {}}
+    scenes = rm.bench_scenes()
     out = torch.empty((H, W), dtype=torch.float32, device="cuda")
     body = torch.empty((H, W), dtype=torch.int32, device="cuda")
     depth = torch.empty((H, W), dtype=torch.float64, device="cuda")
@@ -150,42 +109,30 @@ def main(argv=None) -> int:
     with torch.cuda.stream(stream):
         for name, scene in scenes.items():
             ds = DeviceScene(scene)
-
-            def launch_ao(v, stats=None):
-                _abi.check(lib.rg_render_ao_async(ds.handle, W, H, C.byref(whole), C.byref(v), C.c_void_p(out.data_ptr()), hs,
-                                                  C.byref(stats) if stats is not None else None))
-
-            def launch_aov(stats=None):
-                _abi.check(lib.rg_render_aov_async(ds.handle, W, H, C.byref(whole), C.byref(v_bd), hs,
-                                                   C.byref(stats) if stats is not None else None))
-
-            def launch_frame(stats=None):
-                _abi.check(lib.rg_render_tiles_async(ds.handle, W, H, C.byref(whole), C.c_void_p(rgba.data_ptr()), None, hs,
-                                                     C.byref(stats) if stats is not None else None))
-
+            la = rm.Launches(ds, W, H, stream)
             passes = {"ao_k4_inf": _abi.rg_ao(4, 0, INF, 1e-13), "ao_k4_finite": _abi.rg_ao(4, 0, FINITE[name], 1e-13)}
             if not args.ab:
                 passes.update({"ao_k2_inf": _abi.rg_ao(2, 0, INF, 1e-13), "ao_k2_finite": _abi.rg_ao(2, 0, FINITE[name], 1e-13)})
             rays = {}
             for key, v in passes.items():  # one counted launch each: the rays of the class
                 st = _abi.rg_stats()
-                launch_ao(v, st)
+                la.ao(v, out, st)
                 assert st.rays.primary == W * H and st.rays.secondary == 0 and st.rays.shadow % (v.samples ** 2) == 0
                 rays[key] = int(st.rays.shadow)
-            fns = {key: (lambda v=v: launch_ao(v)) for key, v in passes.items()}
+            fns = {key: (lambda v=v: la.ao(v, out)) for key, v in passes.items()}
             if not args.ab:
                 st = _abi.rg_stats()
-                launch_frame(st)
+                la.frame(rgba, stats=st)
                 rays["frame_depth5"] = int(st.rays.primary + st.rays.shadow + st.rays.secondary)
                 frame_shadow = int(st.rays.shadow)
                 rays["aov_body_depth"] = W * H
-                fns["aov_body_depth"] = launch_aov
-                fns["frame_depth5"] = launch_frame
-            r = alternate(fns)
+                fns["aov_body_depth"] = lambda: la.aov(v_bd)
+                fns["frame_depth5"] = lambda: la.frame(rgba)
+            r = rm.alternate(fns, batch_ms, args.warmup, args.batches)
             assert ds.stream_status(stream.cuda_stream) == (0, -1)
             row = {}
             for key, ms in r.items():
-                row[key] = _summary(ms)
+                row[key] = summary(ms)
                 row[key]["rays"] = rays[key]
                 row[key]["grays_per_s"] = rays[key] / statistics.median(ms) / 1e6
             if not args.ab:
@@ -206,10 +153,7 @@ def main(argv=None) -> int:
         f.write_text(json.dumps(ab, indent=1) + "\n")
         print(json.dumps({args.key or args.label: ab[args.key or args.label]}))
         return 0
-    outp = Path(args.out)
-    outp.parent.mkdir(parents=True, exist_ok=True)
-    outp.write_text(json.dumps(result, indent=1) + "\n")
-    print(json.dumps(result))
+    rm.write_record(result, args.out)
     if args.readme:
         (profiles / "README.md").write_text(_readme(result, profiles))
     return 0

@@ -23,26 +23,19 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import statistics
 import sys
 from pathlib import Path
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO))
-
-
-def _summary(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "batches": len(ms)}
+import rg_measure as rm
+from rg_measure import REPO, summary
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=str(REPO / "profiles" / "area" / "area_bench.json"))
     ap.add_argument("--parent-lib", default=None, help="a libraingun_hip.so of the parent commit, for the `parent` frame")
-    ap.add_argument("--batches", type=int, default=7, help="timed batches per variant (the median is reported)")
-    ap.add_argument("--per-batch", type=int, default=10, help="frames per timed batch")
-    ap.add_argument("--warmup", type=int, default=2, help="untimed batches first")
+    rm.add_timing_args(ap, batches=7, per_batch=10, warmup=2)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--samples", type=int, default=4)
@@ -52,54 +45,28 @@ def main(argv=None) -> int:
 
     from raingun_amd import _abi
     from raingun_amd.camera import Lens
-    from raingun_amd.scene import DeviceScene, SceneDesc, SphericalLight, load_scene
+    from raingun_amd.scene import DeviceScene, SceneDesc, SphericalLight
 
-    if not torch.cuda.is_available():
-        raise SystemExit("area_bench.py needs a GPU: nothing is measured without one")
+    rm.require_gpu("area_bench.py")
     lib = _abi.lib()
     stream = torch.cuda.Stream()
     hs = C.c_void_p(stream.cuda_stream)
     W, H, K = args.width, args.height, args.samples
 
-    def batch_ms(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(args.per_batch):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.per_batch
-
-    def alternate(fns):
-        for fn in fns.values():
-            for _ in range(args.warmup):
-                batch_ms(fn)
-        res = {k: [] for k in fns}
-        for _ in range(args.batches):
-            for k, fn in fns.items():
-                res[k].append(batch_ms(fn))
-        return res
-
-    golden = REPO / "tests" / "golden"
-    test1 = load_scene(golden / "examples" / "test1.yml", texture_root=golden)
-    test1.max_recursion_depth = 5
+    test1 = rm.bench_scenes()["test1"]
     spherical = [isinstance(l, SphericalLight) for l in test1.lights]
     radii = [r if s else 0.0 for r, s in zip((1.0, 1.0, 5.0), spherical)]
     assert len(spherical) == 3 and sum(spherical) == 2
     variants = {"area": (radii, None), "area_lens": (radii, Lens(2.0, 30.0)), "point": (None, None)}
     bufs = {v: torch.empty((H, W, 4), dtype=torch.uint8, device="cuda") for v in (*variants, "parent")}
-    dss = {}
+    dss, la = {}, {}
     for v, (r, lens) in variants.items():
         ds = DeviceScene(test1)
         ds.set_lens(lens)
         ds.set_light_radii(r)
-        dss[v] = ds
+        dss[v], la[v] = ds, rm.Launches(ds, W, H, stream)
 
-    def launch(v, stats=None):
-        _abi.check(lib.rg_render_aa_async(dss[v].handle, W, H, K, C.c_void_p(bufs[v].data_ptr()), None, hs,
-                                          C.byref(stats) if stats is not None else None), "rg_render_aa_async")
-
-    fns = {v: (lambda v=v: launch(v)) for v in variants}
+    fns = {v: (lambda v=v: la[v].aa(K, bufs[v])) for v in variants}
     parent = None
     if args.parent_lib:  # the other build, beside this one: the three entries the frame needs
         parent = C.CDLL(str(Path(args.parent_lib).resolve()))
@@ -118,7 +85,7 @@ def main(argv=None) -> int:
 
     stats = {v: _abi.rg_stats() for v in variants}
     for v in variants:
-        launch(v, stats[v])
+        la[v].aa(K, bufs[v], stats=stats[v])
     if parent is not None:
         fns["parent"]()
     torch.cuda.synchronize()
@@ -126,14 +93,13 @@ def main(argv=None) -> int:
     assert differ > 0, "the radii changed no pixel"
     if parent is not None:
         assert bool((bufs["parent"] == bufs["point"]).all().item()), "the point-light frame is not the parent's"
-    r = alternate(fns)
+    r = rm.alternate(fns, rm.event_batch_ms(stream, args.per_batch), args.warmup, args.batches)
     med = {v: statistics.median(r[v]) for v in fns}
-    result = {"device": torch.cuda.get_device_name(0), "per_batch": args.per_batch, "batches": args.batches,
-              "width": W, "height": H, "samples": K, "max_depth": 5, "scene": "test1", "radii": radii,
+    result = {**rm.header(args, W, H), "samples": K, "max_depth": 5, "scene": "test1", "radii": radii,
               "lens": {"aperture": 2.0, "focus": 30.0},
               "pixels_that_differ_from_the_point_lights": differ,
               "rays": {v: stats[v].rays.as_dict() for v in variants},
-              **{v: _summary(r[v]) for v in fns},
+              **{v: summary(r[v]) for v in fns},
               "area_over_point": med["area"] / med["point"],
               "area_lens_over_point": med["area_lens"] / med["point"]}
     if parent is not None:
@@ -143,10 +109,7 @@ def main(argv=None) -> int:
     for ds in dss.values():
         ds.close()
 
-    outp = Path(args.out)
-    outp.parent.mkdir(parents=True, exist_ok=True)
-    outp.write_text(json.dumps(result, indent=1) + "\n")
-    print(json.dumps(result))
+    rm.write_record(result, args.out)
     return 0
 
 

@@ -21,27 +21,19 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import math
 import statistics
 import sys
 import time
-from pathlib import Path
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO))
-
-
-def _summary(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "batches": len(ms)}
+import rg_measure as rm
+from rg_measure import REPO, summary
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=str(REPO / "profiles" / "camera" / "camera_bench.json"))
-    ap.add_argument("--batches", type=int, default=7, help="timed batches per variant (the median is reported)")
-    ap.add_argument("--per-batch", type=int, default=10, help="frames per timed batch")
-    ap.add_argument("--warmup", type=int, default=3, help="untimed batches first")
+    rm.add_timing_args(ap, batches=7, per_batch=10, warmup=3)
     ap.add_argument("--orbit-frames", type=int, default=64)
     ap.add_argument("--in-flight", type=int, default=8)
     args = ap.parse_args(argv)
@@ -50,42 +42,17 @@ def main(argv=None) -> int:
 
     from raingun_amd import _abi
     from raingun_amd.camera import Camera
-    from raingun_amd.scene import DeviceScene, load_scene
-    from raingun_amd.synth import synthetic_scene
+    from raingun_amd.scene import DeviceScene
 
-    if not torch.cuda.is_available():
-        raise SystemExit("camera_bench.py needs a GPU: nothing is measured without one")
+    rm.require_gpu("camera_bench.py")
     lib = _abi.lib()
     stream = torch.cuda.Stream()
-    hs = C.c_void_p(stream.cuda_stream)
     W, H = 3840, 2160
     whole = _abi.rg_tiling(H, 1, 0)
 
-    def batch_ms(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(args.per_batch):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.per_batch
-
-    def alternate(fns):
-        for fn in fns.values():
-            for _ in range(args.warmup):
-                batch_ms(fn)
-        res = {k: [] for k in fns}
-        for _ in range(args.batches):
-            for k, fn in fns.items():
-                res[k].append(batch_ms(fn))
-        return res
-
-    result = {"device": torch.cuda.get_device_name(0), "per_batch": args.per_batch, "batches": args.batches,
-              "width": W, "height": H, "identity_camera": {}, "orbit": {}}
-    golden = REPO / "tests" / "golden"
-    test1 = load_scene(golden / "examples" / "test1.yml", texture_root=golden)
-    test1.max_recursion_depth = 5
-    scenes = {"test1": test1, "north_star_1024_spheres": synthetic_scene(1024, 2, 5)}
+    batch_ms = rm.event_batch_ms(stream, args.per_batch)
+    result = {**rm.header(args, W, H), "identity_camera": {}, "orbit": {}}
+    scenes = rm.bench_scenes()
     buf = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda")
     buf2 = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda")
 
@@ -93,22 +60,19 @@ def main(argv=None) -> int:
     for name, scene in scenes.items():
         fixed, moved = DeviceScene(scene), DeviceScene(scene)
         moved.set_camera(Camera.identity())
-
-        def launch(ds, out, stats=None):
-            _abi.check(lib.rg_render_tiles_async(ds.handle, W, H, C.byref(whole), C.c_void_p(out.data_ptr()), None, hs,
-                                                 C.byref(stats) if stats is not None else None))
-
+        lf, lm = rm.Launches(fixed, W, H, stream), rm.Launches(moved, W, H, stream)
         st0, st1 = _abi.rg_stats(), _abi.rg_stats()
-        launch(fixed, buf, st0)
+        lf.frame(buf, stats=st0)
         plain = fixed.last_plain()
-        launch(moved, buf2, st1)
+        lm.frame(buf2, stats=st1)
         assert torch.equal(buf, buf2), "the identity camera's frame differs"
         assert st0.rays.as_dict() == st1.rays.as_dict()
-        r = alternate({"fixed": lambda: launch(fixed, buf), "camera": lambda: launch(moved, buf2)})
+        r = rm.alternate({"fixed": lambda: lf.frame(buf), "camera": lambda: lm.frame(buf2)},
+                         batch_ms, args.warmup, args.batches)
         f_ms, c_ms = statistics.median(r["fixed"]), statistics.median(r["camera"])
         result["identity_camera"][name] = {
             "max_depth": 5, "rays": st0.rays.total(), "fixed_view_ran_plain": bool(plain),
-            "fixed_view": _summary(r["fixed"]), "identity_camera": _summary(r["camera"]),
+            "fixed_view": summary(r["fixed"]), "identity_camera": summary(r["camera"]),
             "camera_over_fixed": c_ms / f_ms, "camera_minus_fixed_ms": c_ms - f_ms,
         }
         fixed.close()
@@ -167,19 +131,16 @@ def main(argv=None) -> int:
         assert st == 0, (st, px)
     result["orbit"] = {
         "scene": "north_star_1024_spheres", "frames": n, "in_flight": depth, "radius": radius,
-        "orbit_ms_per_frame": _summary(res["camera"][0]),
+        "orbit_ms_per_frame": summary(res["camera"][0]),
         "orbit_host_enqueue_us_per_frame": statistics.median(res["camera"][1]),
-        "fixed_view_same_loop_ms_per_frame": _summary(res["fixed"][0]),
+        "fixed_view_same_loop_ms_per_frame": summary(res["fixed"][0]),
         "fixed_view_host_enqueue_us_per_frame": statistics.median(res["fixed"][1]),
     }
     for s in streams:
         ds.release_stream(s.cuda_stream)
     ds.close()
 
-    outp = Path(args.out)
-    outp.parent.mkdir(parents=True, exist_ok=True)
-    outp.write_text(json.dumps(result, indent=1) + "\n")
-    print(json.dumps(result))
+    rm.write_record(result, args.out)
     return 0
 
 

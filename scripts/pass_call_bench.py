@@ -18,24 +18,18 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import os
 import statistics
 import sys
 import time
-from pathlib import Path
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO))
+import rg_measure as rm
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None, help="also write the JSON document there")
     ap.add_argument("--label", default="default build")
-    ap.add_argument("--batches", type=int, default=50, help="timed batches per entry and mode")
-    ap.add_argument("--per-batch", type=int, default=10, help="calls per timed batch")
-    ap.add_argument("--warmup", type=int, default=2, help="untimed batches first")
+    rm.add_timing_args(ap, batches=50, per_batch=10, warmup=2)
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--height", type=int, default=180)
     args = ap.parse_args(argv)
@@ -43,19 +37,15 @@ def main(argv=None) -> int:
     import torch
 
     from raingun_amd import _abi
-    from raingun_amd.scene import DeviceScene, load_scene
+    from raingun_amd.scene import DeviceScene
 
-    if not torch.cuda.is_available():
-        raise SystemExit("pass_call_bench.py needs a GPU: nothing is measured without one")
+    rm.require_gpu("pass_call_bench.py")
     lib = _abi.lib()
     stream = torch.cuda.Stream()
     hs = C.c_void_p(stream.cuda_stream)
     W, H = args.width, args.height
     whole = _abi.rg_tiling(H, 1, 0)
-    golden = REPO / "tests" / "golden"
-    scene = load_scene(golden / "examples" / "test1.yml", texture_root=golden)
-    scene.max_recursion_depth = 5
-    ds = DeviceScene(scene)
+    ds = DeviceScene(rm.bench_scenes()["test1"])
 
     def p(t):
         return C.c_void_p(t.data_ptr())
@@ -84,9 +74,7 @@ def main(argv=None) -> int:
         stream.synchronize()
         return (t1 - t0) / args.per_batch * 1e6
 
-    result = {"device": torch.cuda.get_device_name(0), "label": args.label, "width": W, "height": H,
-              "library": os.environ.get("RAINGUN_HIP_LIB", "raingun_amd/libraingun_hip.so"),
-              "per_batch": args.per_batch, "batches": args.batches, "us_per_call": {}}
+    result = {**rm.header(args, W, H), "us_per_call": {}}
     for name, fn in entries.items():
         for mode, s in (("no_stats", None), ("stats", C.byref(st))):
             _abi.check(fn(s))
@@ -96,12 +84,7 @@ def main(argv=None) -> int:
             result["us_per_call"][f"{name} {mode}"] = {"median": statistics.median(us), "min": min(us), "max": max(us)}
     assert ds.stream_status(stream.cuda_stream) == (0, -1)
     ds.close()
-    text = json.dumps(result)
-    print(text)
-    if args.out:
-        out = Path(args.out)
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps(result, indent=1) + "\n")
+    rm.write_record(result, args.out)
     return 0
 
 
